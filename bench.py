@@ -8,7 +8,7 @@ forward, loss, backward, gradient all-reduce (N > 1), clip, SGD step -- the step
 reference's trainer (utils/trainer.py:179-195) plus the input pyramid its DataLoader workers build.
 
     python bench.py [--gpus N --steps K --warmup W] [--workload early|baseline|middle|late]
-                    [--spheres S] [--no-cpu-baseline]
+                    [--spheres S] [--no-cpu-baseline] [--dump-outputs DIR]
 
 N > 1 is launched by torch.distributed.run (one rank per GPU, RCCL): spheres are sharded data
 parallel (weak scaling: S spheres per GPU), gradients all-reduced in one flat bucket.
@@ -51,6 +51,10 @@ def parse():
     ap.add_argument("--no-graph", dest="graph", action="store_false")
     ap.add_argument("--cpu-baseline-steps", type=int, default=20,
                     help="timed iterations per CPU leg (each leg is also cut at a time bound)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, level-0 lengths, the network "
+                         "state it left) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (write_outputs); that "
+                         "step starts from the seeded network and a fresh optimiser, restored outside the timed region")
     return ap.parse_args()
 
 
@@ -187,6 +191,8 @@ def main():
         opt = torch.optim.SGD(groups, lr=cfg.learning_rate, momentum=cfg.momentum, weight_decay=cfg.weight_decay,
                               fused=os.environ.get("MVK_FUSED_SGD", "1") == "1")
     reducer = stepmod.make_reducer(net, cfg, params, world) if (world > 1 or force_dp) else None
+    # --dump-outputs: the seeded network as built, for the last timed step to start from (restore_state)
+    initial = {k: v.detach().clone() for k, v in net.state_dict().items()} if args.dump_outputs else None
 
     # ---- synthetic raw inputs, staged in HBM once (data-parallel: different spheres per rank)
     spheres = [syn.raw_sphere(seed=1000 * rank + i, radius=args.in_radius) for i in range(args.spheres)]
@@ -234,12 +240,26 @@ def main():
         lens, loss = step()
     sync()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    paused = 0.0
+    for i in range(args.steps):
+        if initial is not None and i == args.steps - 1:
+            # The state a step starts from is the product of every earlier step, and two runs of one build do not train
+            # alike: float-atomic sums differ in the last bit, a LeakyReLU input within an ulp of zero then takes the
+            # other slope in the backward, and the run's ~45 steps compound that (the same spread with
+            # MVK_DETERMINISTIC=1, where MIOpen's convolutions still vary). So the dumped step starts from what is
+            # the same in every run -- the seeded network, a fresh optimiser -- on its own batch; the restore is not timed.
+            sync()
+            tp = time.perf_counter()
+            restore_state(net, opt, initial)
+            sync()
+            paused += time.perf_counter() - tp
         lens, loss = step()
     sync()
-    dt = time.perf_counter() - t0
+    dt = time.perf_counter() - t0 - paused
     if hasattr(step, "finish"):
         step.finish()                           # loud check of the input chain's status words
+    # (before the eager drop-in timing below: it trains the same network further)
+    dumped = snapshot_outputs(net, loss, lens) if args.dump_outputs and rank == 0 else None
     eager_ms = None
     if rank == 0 and world == 1 and not force_dp and not args.no_eager_line:
         eager_ms = eager_dropin_ms(ops, eager_step, net_step, lambda: syn.build_batch(cfg, staged, limits, torch.int32)[0])
@@ -300,6 +320,8 @@ def main():
         detail = {"execution": execution_text, "eager_dropin_ms_per_step": eager_ms, "roofline_detail": roofline_detail(prof),
                   "gather_launches": gather_by_level(prof), "cpu_baseline_detail": CPU_DETAIL.get("last")}
         write_detail(res, detail)
+        if dumped is not None:
+            write_outputs(args.dump_outputs, dumped)
         print(result_line(res))
     if world > 1 or force_dp:
         dist.barrier()
@@ -384,6 +406,49 @@ def write_detail(res, detail):
             json.dump({"line": _short(res), "detail": _short(detail)}, f, indent=1)
     except OSError as e:
         print("bench.py: could not write %s: %s" % (path, e), file=sys.stderr)
+
+
+def restore_state(net, opt, initial):
+    """In place (the captured graphs hold these addresses): every state-dict entry back to `initial`, every momentum
+    buffer to zero -- what a fresh optimiser starts from (m = momentum * 0 + d on the first step)."""
+    with torch.no_grad():
+        for k, v in net.state_dict().items():
+            v.copy_(initial[k])
+        for s in opt.state.values():
+            if s.get("momentum_buffer") is not None:
+                s["momentum_buffer"].zero_()
+
+
+def snapshot_outputs(net, loss, lens):
+    """--dump-outputs: what the last timed step hands its caller, copied to the host -- the loss, the level-0 lengths of
+    its batch, and the network it leaves: every state-dict entry ("state.<name>": parameters, BatchNorm running
+    statistics) except the frozen 2D encoder's, which no step changes. Floating tensors as float32, integer ones as
+    float64 (exact)."""
+    out = [("loss", loss.detach().float().reshape(1).cpu().numpy()), ("lens", np.asarray(lens, np.float64))]
+    for name, v in net.state_dict().items():
+        if not name.startswith("net_2d."):
+            out.append(("state." + name, v.detach().cpu().numpy().astype(np.float32 if v.is_floating_point() else np.float64)))
+    return out
+
+
+DUMP_LIMIT = 60 << 20      # bytes of array data: under the 64 MB cap of --dump-outputs with room for the .npy headers
+DUMP_WHOLE = 4096          # arrays of up to this many elements are always written whole
+
+
+def write_outputs(path, arrays, limit=DUMP_LIMIT):
+    """Each (name, array) as <path>/<name>.npy. Everything whole when the arrays fit in `limit` bytes; otherwise arrays
+    of up to DUMP_WHOLE elements stay whole and every larger one keeps the same fraction of its elements (flattened),
+    at positions drawn by a generator seeded with its name: the same positions in every run and every build."""
+    import zlib
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for _, a in arrays)
+    small = sum(a.nbytes for _, a in arrays if a.size <= DUMP_WHOLE)
+    frac = 1.0 if total <= limit else max(limit - small, 0) / float(total - small)
+    for name, a in arrays:
+        if frac < 1.0 and a.size > DUMP_WHOLE:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, size=int(a.size * frac), replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def gather_by_level(prof):

@@ -78,6 +78,19 @@ def g1_subsample():
     save("g1_sub_maxp", points=p, lens=lens, dl=np.float32(0.1), max_p=np.int32(150), out_points=sp, out_lens=sl)
 
 
+def g1b_subsample_cases():
+    """The reference core's output on the random clouds of test_subsample_against_live_reference_if_built (drawn there
+    from the stored seed, not stored): the test compares against it where no compiled reference is present."""
+    assert cport.ref() is not None, "build oracle/_ref first (make -C oracle ref)"
+    cases = [(1, 0.1), (13, 0.5), (14, 0.01), (777, 0.05), (50000, 0.03)]
+    rng = np.random.default_rng(7)
+    arrs = {"seed": np.int64(7), "n": np.array([n for n, _ in cases], np.int32), "dl": np.array([dl for _, dl in cases])}
+    for i, (n, dl) in enumerate(cases):
+        p = (rng.random((n, 3)) * [3, 2, 1]).astype(np.float32)
+        arrs["out_points_%d" % i], arrs["out_lens_%d" % i] = cport.subsample_batch(p, [n], dl=dl, impl="ref")
+    save("g1b_sub_cases", **arrs)
+
+
 def assert_tie_free(q, s, ql, sl, r, allow=False):
     """Count rows holding equal-d2 pairs (the reference order inside such a tie group is
     std::sort-over-KD-tree-traversal defined, i.e. unspecified). Conv fixtures (q == s) must be
@@ -970,7 +983,7 @@ def g13_full_size_gradients():
         save(name, **arrs)
 
 
-GROUPS = {"g13": g13_full_size_gradients, "g12": g12_fusion_wirings, "g11": g11_unproject_select, "g9": g9_ply, "g8": g8_metrics, "g7": g7_sphere_picking, "g1": g1_subsample, "g2": g2_neighbors, "g3": g3_pyramid, "g4": g4_kpconv, "g5": g5_kpfcnn, "g5b": g5b_kpfcnn_deformable, "g10": g10_reprojection,
+GROUPS = {"g13": g13_full_size_gradients, "g12": g12_fusion_wirings, "g11": g11_unproject_select, "g9": g9_ply, "g8": g8_metrics, "g7": g7_sphere_picking, "g1": g1_subsample, "g1b": g1b_subsample_cases, "g2": g2_neighbors, "g3": g3_pyramid, "g4": g4_kpconv, "g5": g5_kpfcnn, "g5b": g5b_kpfcnn_deformable, "g10": g10_reprojection,
           "g6": g6_fusion}
 
 if __name__ == "__main__":

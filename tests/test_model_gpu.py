@@ -537,15 +537,18 @@ def test_graph_capture_refuses_the_default_stream():
                               [], None, None)
 
 
-def test_bench_emits_one_valid_json_line():
+def test_bench_emits_one_valid_json_line(tmp_path):
     """bench.py end to end (default workload, few steps): exactly one JSON line on stdout carrying the
-    contract's keys, the roofline and cpu_baseline objects, no capacity overflow."""
+    contract's keys, the roofline and cpu_baseline objects, no capacity overflow; --dump-outputs writes the last
+    timed step's loss and the network state it left, float32 / float64, within 64 MB."""
+    import glob
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1"],
+    dump = str(tmp_path / "outputs")
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", dump],
                        capture_output=True, text=True, timeout=300, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -564,6 +567,44 @@ def test_bench_emits_one_valid_json_line():
     assert detail["line"]["value"] == d["value"] and len(detail["detail"]["gather_launches"]) >= 5
     c = d["cpu_baseline"]
     assert c["kind"] in ("port", "reference") and c["unit"] == "points/s" and c["cores"] >= 1 and c["value"] > 0
+    files = glob.glob(os.path.join(dump, "*.npy"))
+    assert sum(os.path.getsize(f) for f in files) <= 64e6
+    out = {os.path.basename(f)[:-4]: np.load(f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in out.values())
+    assert abs(float(out["loss"][0]) - d["config"]["final_loss"]) <= 1e-5 * abs(d["config"]["final_loss"])     # (6 digits)
+    assert float(out["lens"].sum()) == d["config"]["points_per_step_per_gpu"]
+    assert any(n.startswith("state.") and n.endswith("KPConv.weights") for n in out)
+
+
+def test_bench_dump_outputs_are_the_same_in_two_runs(tmp_path):
+    """Two runs of bench.py with the same arguments dump the same outputs up to the rounding of one step: the dumped step
+    starts from the seeded network and a fresh optimiser (the trained state of two runs is not the same -- see bench.py).
+    The loss within 1e-6; every other array within 1e-4 of its largest element plus 1e-7: in one step a LeakyReLU input
+    within an ulp of zero (float-atomic sums) may take the other slope in the backward and change a weight gradient's
+    terms of that row (measured: 1e-5 of a KPConv weight array after the step's learning rate), and a BatchNorm bias after
+    its first step is the learning rate times a sum that cancels to ~1e-4 of its terms (last bits 1e-8 apart)."""
+    import glob
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = [str(tmp_path / ("run%d" % i)) for i in range(2)]
+    for d in dumps:
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                            "--no-eager-line", "--dump-outputs", d],
+                           capture_output=True, text=True, timeout=240, cwd=root,
+                           env=dict(os.environ, MVK_BENCH_DETAIL=str(tmp_path / "detail.json")))
+        assert p.returncode == 0, p.stderr[-2000:]
+    names = sorted(os.path.basename(f) for f in glob.glob(os.path.join(dumps[0], "*.npy")))
+    assert names and names == sorted(os.path.basename(f) for f in glob.glob(os.path.join(dumps[1], "*.npy")))
+    worst = []
+    for n in names:
+        a, b = (np.load(os.path.join(d, n)).astype(np.float64) for d in dumps)
+        assert a.shape == b.shape, n
+        bound = 1e-6 * abs(float(b[0])) if n == "loss.npy" else 1e-4 * np.abs(b).max() + 1e-7
+        excess = np.abs(a - b).max() - bound if a.size else -1.0
+        worst.append((excess, n))
+    assert max(worst)[0] <= 0, sorted(worst)[-5:]
 
 
 def test_dataloader_workers_build_the_pyramid_without_forking(tmp_path):
