@@ -8,11 +8,16 @@ forward, loss, backward, gradient all-reduce (N > 1), clip, SGD step -- the step
 reference's trainer (utils/trainer.py:179-195) plus the input pyramid its DataLoader workers build.
 
     python bench.py [--gpus N --steps K --warmup W] [--workload early|baseline|middle|late]
-                    [--spheres S] [--no-cpu-baseline] [--dump-outputs DIR]
+                    [--spheres S] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-eager-line]]
 
 N > 1 is launched by torch.distributed.run (one rank per GPU, RCCL): spheres are sharded data
 parallel (weak scaling: S spheres per GPU), gradients all-reduced in one flat bucket.
 Rank 0 prints ONE JSON line (see DESIGN.md section "Measurement").
+
+A plain run does what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print the line.
+--full adds everything else: the gather roofline and MFMA contraction figures (HIP events around the launches of
+the sixteen eager passes in front of the capture), the eager drop-in step timing, the CPU baseline, and the side
+file bench_detail.json.
 """
 import argparse
 import json
@@ -40,12 +45,15 @@ def parse():
     ap.add_argument("--views", type=int, default=3)
     ap.add_argument("--in-radius", type=float, default=1.2, help="sphere radius (1.2 -> ~20 k points, 1.7 -> ~40 k)")
     ap.add_argument("--deformable", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure beyond the headline: roofline and contraction figures from instrumented eager passes, "
+                         "the eager drop-in step timing, the CPU baseline, bench_detail.json (off: the line's headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--dev", action="store_true",
                     help="development run: accept the knobs that change what a captured step contains (MVK_BENCH_DIAG, "
                          "MVK_BENCH_SKIP, MVK_BENCH_DUMMY_LAUNCHES); without it they are refused")
     ap.add_argument("--no-eager-line", action="store_true",
-                    help="skip the eager drop-in step timing that goes to bench_detail.json")
+                    help="with --full: skip the eager drop-in step timing that goes to bench_detail.json")
     ap.add_argument("--graph", dest="graph", action="store_true", default=None,
                     help="replay the network part (fwd+loss+bwd+clip+SGD) as one hipGraph over capacity-padded levels")
     ap.add_argument("--no-graph", dest="graph", action="store_false")
@@ -215,8 +223,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- warm-up (eager). The gather launches of these steps are timed with HIP events on the
-    #      launch stream for the roofline figure (a captured graph cannot carry timing events).
+    # ---- warm-up (eager). The gather launches of the sixteen passes after it are timed with HIP events on the
+    #      launch stream for the roofline figure (a captured graph cannot carry timing events). A plain run makes the
+    #      same instrumented passes, reads their events back and reports none of their figures: the passes train the
+    #      network and draw the grid orientations the timed steps start from, and plain runs without the events, or
+    #      without their read-back, dumped steps that differed beyond the two-run bound. So every run
+    #      does the same work up to the timed steps.
     use_graph = args.graph if args.graph is not None else True
     for _ in range(max(args.warmup, 1)):
         lens, loss = eager_step()
@@ -261,22 +273,24 @@ def main():
     # (before the eager drop-in timing below: it trains the same network further)
     dumped = snapshot_outputs(net, loss, lens) if args.dump_outputs and rank == 0 else None
     eager_ms = None
-    if rank == 0 and world == 1 and not force_dp and not args.no_eager_line:
+    if args.full and rank == 0 and world == 1 and not force_dp and not args.no_eager_line:
         eager_ms = eager_dropin_ms(ops, eager_step, net_step, lambda: syn.build_batch(cfg, staged, limits, torch.int32)[0])
     if args.dev and os.environ.get("MVK_BENCH_DIAG") == "1" and getattr(step, "state", None):
         h = np.asarray(step.state.get("host", [(0, 0)]))[-args.steps:]
         print("DIAG host ms per step: replay enqueue %.2f | build_async %.2f" % tuple(h.mean(0) * 1e3), file=sys.stderr)
-    # mean real-neighbour counts of every neighbour matrix of this (fixed) synthetic batch, computed
-    # outside the timed region: (Nq, Ns, H) -> H_eff
-    hb, _ = syn.build_batch(cfg, staged, limits, torch.int32)
-    h_eff = {}
-    for l in range(len(hb.points)):
-        ns = hb.points[l].shape[0]
-        for m in (hb.neighbors[l], hb.pools[l]):
-            if m.shape[0] > 0:
-                h_eff[(m.shape[0], ns, m.shape[1])] = float((m < ns).sum().item()) / m.shape[0]
-    prof = ops.profile_collect(h_eff)
-    ops.profile_reset(enabled=False)
+    prof = None
+    if args.full:
+        # mean real-neighbour counts of every neighbour matrix of this (fixed) synthetic batch, computed
+        # outside the timed region: (Nq, Ns, H) -> H_eff
+        hb, _ = syn.build_batch(cfg, staged, limits, torch.int32)
+        h_eff = {}
+        for l in range(len(hb.points)):
+            ns = hb.points[l].shape[0]
+            for m in (hb.neighbors[l], hb.pools[l]):
+                if m.shape[0] > 0:
+                    h_eff[(m.shape[0], ns, m.shape[1])] = float((m < ns).sum().item()) / m.shape[0]
+        prof = ops.profile_collect(h_eff)
+        ops.profile_reset(enabled=False)
 
     t = torch.tensor([dt], device=dev, dtype=torch.float64)
     pts = torch.tensor([float(sum(lens))], device=dev, dtype=torch.float64)
@@ -312,14 +326,15 @@ def main():
                 "final_loss": float(loss.item()),
                 "input_lookahead_batches": int(getattr(step, "lookahead", 0)),
                 "capacity_overflow": bool(getattr(step, "state", {}).get("overflow", False))},
-            "roofline": roofline(prof),
-            "contraction": mfma_report(contraction),
         }
-        if not args.no_cpu_baseline:           # timed on rank 0 at N = 1 only (the other ranks would sit in the barrier)
-            res["cpu_baseline"] = cpu_baseline(cfg, net, staged, limits, spheres, args) if world == 1 else None
-        detail = {"execution": execution_text, "eager_dropin_ms_per_step": eager_ms, "roofline_detail": roofline_detail(prof),
-                  "gather_launches": gather_by_level(prof), "cpu_baseline_detail": CPU_DETAIL.get("last")}
-        write_detail(res, detail)
+        if args.full:
+            res["roofline"] = roofline(prof)
+            res["contraction"] = mfma_report(contraction)
+            if not args.no_cpu_baseline:       # timed on rank 0 at N = 1 only (the other ranks would sit in the barrier)
+                res["cpu_baseline"] = cpu_baseline(cfg, net, staged, limits, spheres, args) if world == 1 else None
+            detail = {"execution": execution_text, "eager_dropin_ms_per_step": eager_ms, "roofline_detail": roofline_detail(prof),
+                      "gather_launches": gather_by_level(prof), "cpu_baseline_detail": CPU_DETAIL.get("last")}
+            write_detail(res, detail)
         if dumped is not None:
             write_outputs(args.dump_outputs, dumped)
         print(result_line(res))

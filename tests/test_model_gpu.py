@@ -538,42 +538,62 @@ def test_graph_capture_refuses_the_default_stream():
 
 
 def test_bench_emits_one_valid_json_line(tmp_path):
-    """bench.py end to end (default workload, few steps): exactly one JSON line on stdout carrying the
-    contract's keys, the roofline and cpu_baseline objects, no capacity overflow; --dump-outputs writes the last
-    timed step's loss and the network state it left, float32 / float64, within 64 MB."""
+    """bench.py end to end (default workload, few steps), once plain and once with --full: exactly one JSON line on
+    stdout carrying the contract's keys, no capacity overflow; with --full also the roofline and cpu_baseline objects
+    and the detail file, without it neither. --dump-outputs writes the last timed step's loss and the network state it
+    left, float32 / float64, within 64 MB. The plain run dumps what the full run does -- both time the same steps -- within
+    the bounds of two runs of one command (test_bench_dump_outputs_are_the_same_in_two_runs)."""
     import glob
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    dump = str(tmp_path / "outputs")
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", dump],
-                       capture_output=True, text=True, timeout=300, cwd=root)
-    assert p.returncode == 0, p.stderr[-2000:]
-    lines = [l for l in p.stdout.splitlines() if l.strip()]
-    assert len(lines) == 1, p.stdout[-2000:]
-    assert len(lines[0]) < 4096, len(lines[0])      # the driver's consumer keeps a bounded tail (BENCH_r02 was not parsed)
-    d = json.loads(lines[0])
-    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
-              "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
+
+    def run(kind, *extra):
+        dump, detail = str(tmp_path / ("outputs_" + kind)), str(tmp_path / ("detail_" + kind + ".json"))
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", dump] + list(extra),
+                           capture_output=True, text=True, timeout=300, cwd=root, env=dict(os.environ, MVK_BENCH_DETAIL=detail))
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, p.stdout[-2000:]
+        assert len(lines[0]) < 4096, len(lines[0])      # the driver's consumer keeps a bounded tail (BENCH_r02 was not parsed)
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                  "vs_baseline", "dtype", "data", "config"):
+            assert k in d, k
+        assert d["n_gpus"] == 1 and d["steps"] == 3 and d["unit"] == "points/s" and d["vs_baseline"] is None
+        assert d["value"] > 5e4 and d["config"]["execution"].startswith("hipGraph") and d["config"]["capacity_overflow"] is False
+        files = glob.glob(os.path.join(dump, "*.npy"))
+        assert sum(os.path.getsize(f) for f in files) <= 64e6
+        out = {os.path.basename(f)[:-4]: np.load(f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in out.values())
+        assert abs(float(out["loss"][0]) - d["config"]["final_loss"]) <= 1e-5 * abs(d["config"]["final_loss"])     # (6 digits)
+        assert float(out["lens"].sum()) == d["config"]["points_per_step_per_gpu"]
+        assert any(n.startswith("state.") and n.endswith("KPConv.weights") for n in out)
+        return d, out, detail
+
+    plain, plain_out, plain_detail = run("plain")
+    d, full_out, detail_path = run("full", "--full")
+    for k in ("roofline", "cpu_baseline"):
         assert k in d, k
-    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["unit"] == "points/s" and d["vs_baseline"] is None
-    assert d["value"] > 5e4 and d["config"]["execution"].startswith("hipGraph") and d["config"]["capacity_overflow"] is False
     r = d["roofline"]
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-5     # (6 significant digits in the line)
     assert r["kernel"].startswith("kpconv_gather_") and 0.2 < r["frac"] < 1.0
-    detail = json.load(open(os.path.join(root, "gpurun_out", "bench_detail.json")))
+    detail = json.load(open(detail_path))
     assert detail["line"]["value"] == d["value"] and len(detail["detail"]["gather_launches"]) >= 5
     c = d["cpu_baseline"]
     assert c["kind"] in ("port", "reference") and c["unit"] == "points/s" and c["cores"] >= 1 and c["value"] > 0
-    files = glob.glob(os.path.join(dump, "*.npy"))
-    assert sum(os.path.getsize(f) for f in files) <= 64e6
-    out = {os.path.basename(f)[:-4]: np.load(f) for f in files}
-    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in out.values())
-    assert abs(float(out["loss"][0]) - d["config"]["final_loss"]) <= 1e-5 * abs(d["config"]["final_loss"])     # (6 digits)
-    assert float(out["lens"].sum()) == d["config"]["points_per_step_per_gpu"]
-    assert any(n.startswith("state.") and n.endswith("KPConv.weights") for n in out)
+
+    assert not {"roofline", "contraction", "cpu_baseline"} & set(plain) and not os.path.exists(plain_detail)
+    assert plain["config"]["points_per_step_per_gpu"] == d["config"]["points_per_step_per_gpu"]
+    assert sorted(plain_out) == sorted(full_out)
+    for n, b in full_out.items():
+        a, b = plain_out[n].astype(np.float64), b.astype(np.float64)
+        assert a.shape == b.shape, n
+        bound = 1e-6 * abs(float(b[0])) if n == "loss" else 1e-4 * np.abs(b).max() + 1e-7
+        assert not a.size or np.abs(a - b).max() <= bound, (n, float(np.abs(a - b).max()), bound)
 
 
 def test_bench_dump_outputs_are_the_same_in_two_runs(tmp_path):

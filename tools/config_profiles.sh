@@ -18,7 +18,7 @@ one() {
     cd $R
     echo; echo "# bench line of the same workload without a profiler, and its gather launches (forward gathers; [dx] = gather-form feature"
     echo "# gradients over the reverse lists) with algorithmic GB/s and the fraction of the 8 TB/s HBM peak:"
-    python3 bench.py --no-cpu-baseline --no-eager-line "$@" 2>/dev/null | tail -1
+    python3 bench.py --full --no-cpu-baseline --no-eager-line "$@" 2>/dev/null | tail -1
     python3 - <<'PY'
 import json
 d = json.load(open("gpurun_out/bench_detail.json"))

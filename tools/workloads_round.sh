@@ -1,6 +1,6 @@
 # usage (GPU box): bash tools/workloads_round.sh  -- the bench line of every workload of DESIGN.md's tables (short form)
 R=$GRAFT_REPO_ROOT
-run() { echo "== $*"; python3 $R/bench.py --no-cpu-baseline --steps 30 "$@" 2>/dev/null | python3 -c "
+run() { echo "== $*"; python3 $R/bench.py --full --no-cpu-baseline --steps 30 "$@" 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d['roofline']; c = d.get('contraction') or {}
