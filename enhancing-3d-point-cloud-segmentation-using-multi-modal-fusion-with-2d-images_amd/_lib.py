@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmvkpconv.so")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
@@ -149,6 +149,10 @@ _SIGNATURES = {
     "mvk_group_points_bwd": (C.c_int, [_vp, _vp, _i, _i, _i64, _i64, _i, _vp, _vp]),
     "mvk_group_points_fwd_f64": (C.c_int, [_vp, _vp, _i, _i, _i64, _i64, _i, _vp, _vp]),
     "mvk_group_points_bwd_f64": (C.c_int, [_vp, _vp, _i, _i, _i64, _i64, _i, _vp, _vp]),
+    "mvk_vote_update": (C.c_int, [_vp, _i64, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, C.c_double, C.c_double,
+                                  _f, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    "mvk_vote_predict": (C.c_int, [_vp, _i64, _i, _vp, _i, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "mvk_affine_lrelu": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i, _f, _vp, _vp]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

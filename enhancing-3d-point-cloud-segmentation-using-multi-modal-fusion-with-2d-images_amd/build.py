@@ -29,6 +29,7 @@ SOURCES = [
     ("subsample.hip", ["-ffp-contract=off"]),
     ("neighbors.hip", ["-ffp-contract=off"]),
     ("fusion.hip", ["-ffp-contract=off"]),
+    ("vote.hip", ["-ffp-contract=off"]),      # float64 vote update in two roundings, like NumPy
 ]
 
 

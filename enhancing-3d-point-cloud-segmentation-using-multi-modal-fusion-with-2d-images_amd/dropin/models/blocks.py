@@ -50,6 +50,52 @@ def _bn_rows(x, module, use_bn=True):
 _MFMA_LINEAR = os.environ.get("MVK_MFMA_LINEAR", "1") == "1"
 
 
+# ---------------------------------------------------------------- frozen inference (no reference counterpart)
+
+def _frozen(module):
+    """The snapshot freeze_inference left on this block, when it applies: the block is frozen, in eval mode, and no
+    gradient is being recorded. None in every other situation (the block then runs exactly as if never frozen)."""
+    fz = module.__dict__.get('_frozen')
+    if fz is None or module.training or torch.is_grad_enabled():
+        return None
+    return fz
+
+
+def freeze_inference(net):
+    """Snapshot the BatchNorm statistics of every block of `net` for inference: each BatchNormBlock with use_bn keeps
+    scale = gamma / sqrt(running_var + eps) and shift = beta - running_mean * scale, each UnaryBlock also its weight
+    pre-multiplied by scale. In eval mode under torch.no_grad() a BatchNormBlock is then ONE launch (ops.affine_lrelu:
+    scale, shift, residual addend and LeakyReLU) instead of nn.BatchNorm1d plus an activation / join launch, and a
+    UnaryBlock without a join is ONE GEMM with the shift and the activation in its store (ops.linear_bias_lrelu) -- no
+    normalising launch at all. In training mode, or with gradients enabled, nothing changes.
+
+    The snapshot is a plain attribute, not a buffer: state-dict keys stay as they are. It is a copy: after
+    load_state_dict (or any other change of the parameters or running statistics) call freeze_inference again.
+    train(True) on a block drops its snapshot; unfreeze_inference drops all of them. Returns net."""
+    with torch.no_grad():
+        for m in net.modules():
+            if isinstance(m, BatchNormBlock) and m.use_bn and m.batch_norm.running_var is not None:
+                bn = m.batch_norm
+                gamma = bn.weight.double() if bn.weight is not None else torch.ones_like(bn.running_var, dtype=torch.float64)
+                beta = bn.bias.double() if bn.bias is not None else torch.zeros_like(gamma)
+                scale = gamma / torch.sqrt(bn.running_var.double() + bn.eps)
+                shift = beta - bn.running_mean.double() * scale
+                m._frozen = (scale.float().contiguous(), shift.float().contiguous(), scale)
+        for m in net.modules():
+            if isinstance(m, UnaryBlock) and m.use_bn and m.batch_norm.__dict__.get('_frozen') is not None:
+                scale = m.batch_norm._frozen[2]
+                m._frozen = (m.mlp.weight.double() * scale[:, None]).float().contiguous()
+    return net
+
+
+def unfreeze_inference(net):
+    """Drop every snapshot of freeze_inference. Returns net."""
+    for m in net.modules():
+        if isinstance(m, (BatchNormBlock, UnaryBlock)):
+            m._frozen = None
+    return net
+
+
 # ---------------------------------------------------------------- simple functions (blocks.py:35-133)
 
 def gather(x, idx, method=2):
@@ -213,10 +259,19 @@ class BatchNormBlock(nn.Module):
     def reset_parameters(self):
         nn.init.zeros_(self.bias)
 
+    def train(self, mode=True):
+        if mode:
+            self._frozen = None         # the snapshot of freeze_inference does not survive a return to training
+        return super(BatchNormBlock, self).train(mode)
+
     def forward(self, x, slope=None, addend=None):
         """slope: when given, the LeakyReLU that follows every BatchNormBlock in the reference's blocks
         is applied here (fused into the masked kernel in capacity-padded mode). addend: the shortcut of a
         residual block, added before that activation (blocks.py:649), in the same launch when masked."""
+        fz = _frozen(self)
+        if fz is not None and x.is_cuda and x.dim() == 2:
+            # frozen statistics: scale, shift, join and activation in one launch (freeze_inference)
+            return ops.affine_lrelu(x, fz[0], fz[1], 1.0 if slope is None else slope, addend)
         if self.use_bn:
             n_valid = _bn_rows(x, self)
             if n_valid is not None:
@@ -253,6 +308,11 @@ class UnaryBlock(nn.Module):
         if not no_relu:
             self.leaky_relu = nn.LeakyReLU(0.1)
 
+    def train(self, mode=True):
+        if mode:
+            self._frozen = None         # see BatchNormBlock.train
+        return super(UnaryBlock, self).train(mode)
+
     def forward(self, x, batch=None, join=None, passthrough=False):
         """join = (shortcut, slope): finish a residual block here -- LeakyReLU_slope(BN(x W^T) + shortcut).
         passthrough: returns (output, x') where x' aliases x for the block's shortcut branch: the gradients of the two
@@ -260,6 +320,11 @@ class UnaryBlock(nn.Module):
         # nn.Linear(bias=False) = x @ W^T: on the f32 MFMA GEMM (faster than the library GEMM on these
         # tall-skinny shapes, tools/gemm_bench.py); parameters stay those of self.mlp (state-dict compatible)
         alias = x
+        fz, fz_bn = _frozen(self), self.batch_norm.__dict__.get('_frozen')
+        if fz is not None and fz_bn is not None and join is None and x.is_cuda and x.dim() == 2:
+            # frozen BatchNorm folded into the layer: W * scale in the product, shift and activation in its store
+            y = ops.linear_bias_lrelu(x, fz, fz_bn[1], 1.0 if self.no_relu else 0.1)
+            return (y, alias) if passthrough else y
         if (_MFMA_LINEAR and _FUSED_BIAS and x.is_cuda and not self.use_bn and join is None and not passthrough
                 and x.dim() == 2 and self.out_dim <= 256):
             # BatchNorm-less layer: bias and activation leave with the GEMM's store (ops.linear_bias_lrelu)

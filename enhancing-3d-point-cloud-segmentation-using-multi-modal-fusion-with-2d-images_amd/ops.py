@@ -2477,3 +2477,119 @@ def tukey_update(points, center, radius, potentials):
     check(lib().mvk_tukey_update(_p(pts), pts.shape[0], c.ctypes.data_as(C.c_void_p), float(radius), _p(potentials),
                                  _stream()))
     return potentials
+
+
+# --------------------------------------------------------------------------------------------
+# test-time voting + frozen BatchNorm apply (csrc/vote.hip); forward only, no autograd nodes
+# --------------------------------------------------------------------------------------------
+
+def _i32c(t, what):
+    if t.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError("%s must be int32 or int64" % what)
+    return t.contiguous() if t.dtype == torch.int32 else t.to(torch.int32).contiguous()
+
+
+def vote_update_batch(votes, cloud_offsets, scores, lengths, input_inds, cloud_inds, smooth=0.95, is_logits=True,
+                      points=None, r2_max=0.0, labels=None, label_values=None, col_map=None, confusion=None,
+                      cloud_inds_host=None):
+    """One batch's smoothed votes, in place (tester.py:160-186, trainer.py:351-378): for every row i of sphere b,
+    votes[cloud_offsets[cloud_inds[b]] + input_inds[i]] = smooth * old + (1 - smooth) * p[i] in float64, with p the
+    float32 softmax of scores [N,C] (is_logits) or scores itself. votes [sum of cloud sizes, C] float64 and cloud_offsets
+    [n_clouds + 1] int64, both in HBM. points [N,3] with r2_max > 0: only rows with |p|^2 < r2_max vote. Spheres are applied
+    in batch order; the B integers of cloud_inds are the only thing read on the host (pass cloud_inds_host to skip even
+    that). labels / label_values / col_map / confusion [Ctot,Ctot] int64: also count this batch's own argmax against its
+    labels (trainer.py:395-412)."""
+    _dev(votes, cloud_offsets, scores, lengths, input_inds, cloud_inds, points, labels, label_values, col_map, confusion)
+    if votes.dtype != torch.float64 or votes.dim() != 2 or not votes.is_contiguous():
+        raise RuntimeError("vote_update_batch: votes must be a contiguous float64 [rows, C] tensor")
+    if cloud_offsets.dtype != torch.int64 or cloud_offsets.dim() != 1 or cloud_offsets.shape[0] < 2:
+        raise RuntimeError("vote_update_batch: cloud_offsets must be int64 [n_clouds + 1]")
+    scores = _f32c(scores)
+    N, Cn = scores.shape
+    if Cn != votes.shape[1]:
+        raise RuntimeError("vote_update_batch: scores have %d columns, the votes %d" % (Cn, votes.shape[1]))
+    inds, i64 = _idx(input_inds.reshape(-1))
+    if inds.shape[0] != N:
+        raise RuntimeError("vote_update_batch: input_inds [N] expected")
+    lens = _i32c(lengths.reshape(-1), "lengths")
+    cl = _i32c(cloud_inds.reshape(-1), "cloud_inds")
+    B = lens.shape[0]
+    if cl.shape[0] != B:
+        raise RuntimeError("vote_update_batch: lengths and cloud_inds differ in size")
+    host = _np.ascontiguousarray(cl.cpu().numpy() if cloud_inds_host is None else cloud_inds_host, dtype=_np.int32).reshape(-1)
+    if host.shape[0] != B:
+        raise RuntimeError("vote_update_batch: cloud_inds_host [B] expected")
+    if points is not None:
+        points = _f32c(points)
+        if points.shape != (N, 3):
+            raise RuntimeError("vote_update_batch: points [N,3] expected")
+    lab = l64 = None
+    Ctot = 0
+    if confusion is not None:
+        if labels is None or label_values is None or col_map is None:
+            raise RuntimeError("vote_update_batch: the confusion needs labels, label_values and col_map")
+        lab, l64 = _idx(labels.reshape(-1))
+        Ctot = label_values.shape[0]
+        if (lab.shape[0] != N or label_values.dtype != torch.int32 or col_map.dtype != torch.int32 or
+                col_map.shape[0] != Ctot or confusion.dtype != torch.int64 or tuple(confusion.shape) != (Ctot, Ctot) or
+                not confusion.is_contiguous()):
+            raise RuntimeError("vote_update_batch: labels [N], label_values / col_map [Ctot] int32 and a contiguous "
+                               "int64 confusion [Ctot,Ctot] expected")
+        label_values, col_map = label_values.contiguous(), col_map.contiguous()
+    smooth = float(smooth)
+    check(lib().mvk_vote_update(_p(scores), N, Cn, int(bool(is_logits)), _p(points), _p(lens), B, _p(inds), i64, _p(cl),
+                                host.ctypes.data_as(C.c_void_p), cloud_offsets.shape[0] - 1, _p(cloud_offsets.contiguous()),
+                                _p(votes), smooth, 1 - smooth, float(r2_max), _p(lab), int(l64 or 0),
+                                _p(label_values) if confusion is not None else None,
+                                _p(col_map) if confusion is not None else None, Ctot, _p(confusion), _stream()))
+    return votes
+
+
+def vote_predict(votes, label_values, col_map, proj=None, targets=None, confusion=None):
+    """preds [Nfull] int32 (raw label values) of one cloud's votes [Nc,C] float64: first maximum over the row widened by a
+    zero column per ignored label (col_map [Ctot] int32: model column or -1), through the reprojection proj [Nfull]
+    (int32 / int64) when given (tester.py:223-236, :273-297). targets [Nfull] int32 raw labels: the confusion
+    [Ctot,Ctot] int64 (rows = truth; truths outside label_values dropped) is accumulated into `confusion` (created when
+    None) and returned next to the predictions."""
+    _dev(votes, label_values, col_map, proj, targets, confusion)
+    if votes.dtype != torch.float64 or votes.dim() != 2 or not votes.is_contiguous():
+        raise RuntimeError("vote_predict: votes must be a contiguous float64 [Nc, C] tensor")
+    Ctot = label_values.shape[0]
+    if label_values.dtype != torch.int32 or col_map.dtype != torch.int32 or col_map.shape[0] != Ctot:
+        raise RuntimeError("vote_predict: label_values and col_map must be int32 [Ctot]")
+    p64 = 0
+    if proj is not None:
+        proj, p64 = _idx(proj.reshape(-1))
+    Nfull = votes.shape[0] if proj is None else proj.shape[0]
+    preds = torch.empty((Nfull,), device=votes.device, dtype=torch.int32)
+    if targets is not None:
+        if targets.dtype != torch.int32 or targets.reshape(-1).shape[0] != Nfull:
+            raise RuntimeError("vote_predict: targets must be int32 [Nfull]")
+        targets = targets.reshape(-1).contiguous()
+        if confusion is None:
+            confusion = torch.zeros((Ctot, Ctot), device=votes.device, dtype=torch.int64)
+        elif confusion.dtype != torch.int64 or tuple(confusion.shape) != (Ctot, Ctot) or not confusion.is_contiguous():
+            raise RuntimeError("vote_predict: confusion must be a contiguous int64 [Ctot,Ctot] tensor")
+    check(lib().mvk_vote_predict(_p(votes), votes.shape[0], votes.shape[1], _p(proj), p64, Nfull,
+                                 _p(label_values.contiguous()), _p(col_map.contiguous()), Ctot, _p(targets), _p(preds),
+                                 _p(confusion) if targets is not None else None, _stream()))
+    return preds if targets is None else (preds, confusion)
+
+
+def affine_lrelu(x, scale, shift, slope=1.0, addend=None):
+    """LeakyReLU_slope(x * scale[col] + shift[col] (+ addend)) for rows [R,C] in one launch: a BatchNorm with frozen
+    statistics (scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale), the activation and the
+    residual join after it. Forward only: raises when a gradient would be needed."""
+    if torch.is_grad_enabled() and (x.requires_grad or (addend is not None and addend.requires_grad)):
+        raise RuntimeError("affine_lrelu is forward only (frozen inference): call it under torch.no_grad()")
+    _dev(x, scale, shift, addend)
+    if x.dim() != 2 or scale.shape != (x.shape[1],) or shift.shape != scale.shape:
+        raise RuntimeError("affine_lrelu: x [R,C], scale [C] and shift [C] expected")
+    if addend is not None and addend.shape != x.shape:
+        raise RuntimeError("affine_lrelu: the addend must have the shape of x")
+    x, scale, shift = _f32c(x), _f32c(scale), _f32c(shift)
+    addend = None if addend is None else _f32c(addend)
+    y = torch.empty_like(x)
+    check(lib().mvk_affine_lrelu(_p(x), _p(scale), _p(shift), _p(addend), x.shape[0], x.shape[1], float(slope), _p(y),
+                                 _stream()))
+    return y

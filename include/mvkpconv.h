@@ -19,6 +19,8 @@
  *                             mvpnet/ops/cuda/group_points_kernel.cu:25-145
  *   mvk_knn_f64               KPConv-PyTorch/datasets/ScanNet_sphere_color.py:448-451 (sklearn ball_tree k-NN)
  *   mvk_unproject_depth       KPConv-PyTorch/datasets/ScanNet_sphere_color.py:66-72,409-417
+ *   mvk_vote_*                KPConv-PyTorch/utils/tester.py:160-186,223-236,273-297 and utils/trainer.py:351-378,
+ *                             :395-412,:497-506 (the NumPy voting loops of test and validation)
  */
 #ifndef MVKPCONV_H
 #define MVKPCONV_H
@@ -29,7 +31,7 @@
 extern "C" {
 #endif
 
-#define MVK_ABI_VERSION 8   /* 8: the fp16-feature entry points (mvk_kpconv_gather_fwd_f16 / _ld, mvk_gemm_f16, mvk_gemm_f16_stream / _plan, mvk_round_weights_f16) are gone, mvk_deform_regularizer_many, sorted reverse lists of any width; 7: BatchNorm folded into the GEMMs around it (statistics finished by the producer, apply in the consumer's operand load), reverse lists out of the neighbour search, grouped plan takes the stream; 6: ordered split reductions (mvk_gemm_split_arena), reverse neighbour lists; 5: gather with a work list (mvk_kpconv_gather_fwd_ordered); 4: fp16 mode on gfx950 forms: padded fp16 aggregate rows, streaming contraction (v_mfma_f32_16x16x32_f16) with statistics epilogue, one-launch weight rounding; 3: gemm plan / BatchNorm-statistics epilogue, BatchNorm takes epilogue partials, fused clip + SGD, offset gradient + regulariser, segmentation loss, gather launch plan, strided gather-rows backward, channels-last fusion gather; 2: masked BatchNorm takes the batch counter and a residual addend; enqueue-only / device-lens pyramid entry points; fp16-feature mode; capacity padding */
+#define MVK_ABI_VERSION 9   /* 9: test-time voting (mvk_vote_update, mvk_vote_predict) and the frozen BatchNorm apply (mvk_affine_lrelu); 8: the fp16-feature entry points (mvk_kpconv_gather_fwd_f16 / _ld, mvk_gemm_f16, mvk_gemm_f16_stream / _plan, mvk_round_weights_f16) are gone, mvk_deform_regularizer_many, sorted reverse lists of any width; 7: BatchNorm folded into the GEMMs around it (statistics finished by the producer, apply in the consumer's operand load), reverse lists out of the neighbour search, grouped plan takes the stream; 6: ordered split reductions (mvk_gemm_split_arena), reverse neighbour lists; 5: gather with a work list (mvk_kpconv_gather_fwd_ordered); 4: fp16 mode on gfx950 forms: padded fp16 aggregate rows, streaming contraction (v_mfma_f32_16x16x32_f16) with statistics epilogue, one-launch weight rounding; 3: gemm plan / BatchNorm-statistics epilogue, BatchNorm takes epilogue partials, fused clip + SGD, offset gradient + regulariser, segmentation loss, gather launch plan, strided gather-rows backward, channels-last fusion gather; 2: masked BatchNorm takes the batch counter and a residual addend; enqueue-only / device-lens pyramid entry points; fp16-feature mode; capacity padding */
 
 /* influence / aggregation codes (blocks.py:329-354) */
 #define MVK_INFL_CONSTANT 0
@@ -625,6 +627,47 @@ int mvk_group_points_fwd_f64(const double* points, const int64_t* index, int B, 
                              double* out, void* stream);
 int mvk_group_points_bwd_f64(const double* grad_out, const int64_t* index, int B, int C, int64_t N1, int64_t N2, int K,
                              double* grad_in, void* stream);
+
+/* ---------------- test-time voting (csrc/vote.hip) ------------------------- */
+
+/* One batch's votes (tester.py:160-186, trainer.py:351-378). scores [N,C] f32: logits (is_logits != 0; the softmax is
+ * evaluated in float32, as the reference rounds probabilities to float32 before they reach its float64 arrays) or
+ * probabilities. points [N,3] f32 level-0 coordinates relative to the sphere centre, or NULL; lengths [B] int32;
+ * input_inds [N] int32 / int64 (inds64): row of each point inside its cloud; cloud_inds [B] int32 and cloud_inds_host,
+ * the same B integers on the HOST (they order the launches; nothing sized by N is read back). votes: the float64 votes
+ * of ALL clouds, [cloud_offsets[n_clouds], C] with cloud c at rows cloud_offsets[c] .. cloud_offsets[c+1]
+ * (cloud_offsets [n_clouds+1] int64, DEVICE). For every row i of sphere b with (x*x + y*y) + z*z < r2_max in float32
+ * (r2_max <= 0 or points == NULL: every row):
+ *     votes[off[cloud_inds[b]] + input_inds[i]] = smooth * old + one_minus_smooth * (double)p[i]
+ * in float64, two products and one sum, each rounded (no FMA). one_minus_smooth is passed, not derived: the caller
+ * computes 1 - smooth in double as Python does (1 - 0.95 is not 0.05). Spheres are applied in batch order: the batch is
+ * cut into runs of spheres from pairwise different clouds, one launch per run, so a point shared by two spheres of one
+ * cloud gets both updates, first then second. The indices of ONE sphere must be distinct (they are a radius query's).
+ * An index outside its cloud, or a cloud index outside [0, n_clouds), writes nothing.
+ * confusion != NULL: also the validation loop's per-batch count (trainer.py:395-412) -- argmax (first maximum) of each
+ * row's own probabilities widened through col_map against labels [N] (int32 / int64 by labels64, raw values looked up
+ * in label_values [Ctot]; values outside the table are dropped), accumulated into confusion [Ctot,Ctot] int64, rows =
+ * truth. C <= 64, Ctot <= 64, B <= 4096. Integer atomics only. */
+int mvk_vote_update(const float* scores, int64_t N, int C, int is_logits, const float* points, const int32_t* lengths,
+                    int B, const void* input_inds, int inds64, const int32_t* cloud_inds, const int32_t* cloud_inds_host,
+                    int n_clouds, const int64_t* cloud_offsets, double* votes, double smooth, double one_minus_smooth,
+                    float r2_max, const void* labels, int labels64, const int32_t* label_values, const int32_t* col_map,
+                    int Ctot, int64_t* confusion, void* stream);
+/* Predictions and score of one cloud (tester.py:223-236,273-297; trainer.py:497-506). votes [Nc,C] f64; proj [Nfull]
+ * int32 / int64 (proj64) rows of `votes` for every evaluation point, or NULL (then Nfull == Nc, rows one to one);
+ * label_values [Ctot] int32; col_map [Ctot] int32: the model column of each slot of the full label table, -1 for an
+ * ignored label (where the reference np.inserts a zero column). preds [Nfull] int32 = label_values[first maximum of
+ * the widened row]: a never-visited row predicts label_values[0]; -1 for a proj index outside [0, Nc). targets [Nfull]
+ * int32 raw labels and confusion [Ctot,Ctot] int64 (accumulated; rows = truth, columns = prediction; truths outside
+ * label_values are dropped as confusion_matrix(labels=...) does): both or neither. */
+int mvk_vote_predict(const double* votes, int64_t Nc, int C, const void* proj, int proj64, int64_t Nfull,
+                     const int32_t* label_values, const int32_t* col_map, int Ctot, const int32_t* targets, int32_t* preds,
+                     int64_t* confusion, void* stream);
+/* BatchNorm with frozen statistics, forward only (blocks.py:456-463 in eval mode + the LeakyReLU / residual join
+ * after it): y = LeakyReLU_slope(x * scale[col] + shift[col] (+ addend)) for rows [R,C] f32 in one launch; slope = 1:
+ * no activation; addend [R,C] or NULL. */
+int mvk_affine_lrelu(const float* x, const float* scale, const float* shift, const float* addend, int64_t R, int C,
+                     float slope, float* y, void* stream);
 
 #ifdef __cplusplus
 }
