@@ -153,6 +153,17 @@ _SIGNATURES = {
                                   _f, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "mvk_vote_predict": (C.c_int, [_vp, _i64, _i, _vp, _i, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "mvk_affine_lrelu": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i, _f, _vp, _vp]),
+    "mvk_fps_workspace": (C.c_int64, [_i64, _i64, _i]),
+    "mvk_fps": (C.c_int, [_vp, _i, _i64, _i, _i64, _vp, _vp, _i64, _vp]),
+    "mvk_fps_f64": (C.c_int, [_vp, _i, _i64, _i, _i64, _vp, _vp, _i64, _vp]),
+    "mvk_pn2_ball_query": (C.c_int, [_vp, _vp, _i, _i64, _i64, _f, _i, _vp, _vp, _vp]),
+    "mvk_pn2_ball_query_f64": (C.c_int, [_vp, _vp, _i, _i64, _i64, _f, _i, _vp, _vp, _vp]),
+    "mvk_knn_distance": (C.c_int, [_vp, _vp, _i, _i64, _i64, _i, _vp, _vp, _vp]),
+    "mvk_knn_distance_f64": (C.c_int, [_vp, _vp, _i, _i64, _i64, _i, _vp, _vp, _vp]),
+    "mvk_interpolate_fwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _vp]),
+    "mvk_interpolate_fwd_f64": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _vp]),
+    "mvk_interpolate_bwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _vp]),
+    "mvk_interpolate_bwd_f64": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _vp]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -30,6 +30,7 @@ SOURCES = [
     ("neighbors.hip", ["-ffp-contract=off"]),
     ("fusion.hip", ["-ffp-contract=off"]),
     ("vote.hip", ["-ffp-contract=off"]),      # float64 vote update in two roundings, like NumPy
+    ("pn2.hip", ["-ffp-contract=off"]),       # squared distances in three rounded products and two rounded sums
 ]
 
 

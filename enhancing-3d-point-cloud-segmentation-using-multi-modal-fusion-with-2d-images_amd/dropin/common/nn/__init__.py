@@ -1,10 +1,12 @@
-"""The slice of the reference's ``common.nn`` the fusion path uses (common/nn/modules/mlp.py:38-75,
-common/nn/modules/conv.py:29-51, common/nn/init.py:22-26). 1x1 convolutions and BatchNorm stay
+"""The slice of the reference's ``common.nn`` the fusion path and the MVPNet baseline use
+(common/nn/modules/mlp.py:38-95, common/nn/modules/conv.py:29-51, common/nn/init.py:22-26,
+common/nn/functional.py:128-149). 1x1 convolutions and BatchNorm stay
 PyTorch-ROCm library ops (plain GEMMs)."""
 import warnings
 
 import torch
 from torch import nn
+import torch.nn.functional as F
 
 try:    # submodules the fusion path does not use (common.nn.freezer, .functional, ...) fall through to the reference
     from _fallthrough import extend as _extend
@@ -75,6 +77,42 @@ class SharedMLP(nn.ModuleList):
         for module in self:
             x = module(x)
         return x
+
+
+class SharedMLPDO(SharedMLP):
+    """SharedMLP with dropout after every layer (common/nn/modules/mlp.py:78-95): element dropout on (B,C,N)
+    activations, channel dropout on (B,C,N,K)."""
+
+    _DROPOUT = {1: F.dropout, 2: F.dropout2d}
+
+    def __init__(self, *args, p=0.5, **kwargs):
+        super(SharedMLPDO, self).__init__(*args, **kwargs)
+        self.p = p
+
+    @property
+    def dropout_fn(self):
+        return self._DROPOUT[self.ndim]
+
+    def forward(self, x):
+        drop = self.dropout_fn
+        for layer in self:
+            x = drop(layer(x), self.p, self.training)       # out of place: the ReLU before it works in place
+        return x
+
+    def extra_repr(self):
+        return 'p={}'.format(self.p)
+
+
+def batch_index_select(input, index, dim):
+    """input (b, ...), index (b, n) -> input gathered along `dim` with a separate index row per batch element
+    (common/nn/functional.py:128-149)."""
+    if index.dim() != 2 or input.size(0) != index.size(0):
+        raise ValueError('batch_index_select: index must be (batch, n) with the batch size of input')
+    view = [1] * input.dim()
+    view[0], view[dim] = index.size(0), index.size(1)
+    shape = list(input.shape)
+    shape[dim] = -1
+    return torch.gather(input, dim, index.view(view).expand(shape))
 
 
 def xavier_uniform(module):

@@ -1,6 +1,11 @@
 """FeatureAggregation (reference mvpnet/models/mvpnet_3d.py:12-70): per (point, neighbour) feature
 [feat_2d | dxyz | |dxyz|^2] -> SharedMLP (1x1 conv + BN + ReLU) -> reduction over k.
-Sub-module names (mlp.{i}.conv / mlp.{i}.bn) match the reference so MVPNet checkpoints load."""
+Sub-module names (mlp.{i}.conv / mlp.{i}.bn) match the reference so MVPNet checkpoints load.
+MVPNet3D (reference :73-135): the baseline's wiring 2D encoder -> unprojection by group_points ->
+FeatureAggregation -> 3D network (PN2SSG)."""
+import logging
+
+import numpy as np
 import torch
 from torch import nn
 import torch.nn.functional as F
@@ -76,3 +81,56 @@ class FeatureAggregation(nn.Module):
         for m in self.modules():
             if isinstance(m, (nn.Conv1d, nn.Conv2d, nn.Linear)):
                 xavier_uniform(m)
+
+
+_log = logging.getLogger(__name__)
+
+
+def _load_encoder_weights(net_2d, path):
+    """The 'model' entry of a training checkpoint of the 2D network, read on the host."""
+    state = torch.load(path, map_location="cpu")['model']
+    net_2d.load_state_dict(state)
+    _log.info("MVPNet3D: 2D encoder weights (%d tensors) taken from %s", len(state), path)
+
+
+class MVPNet3D(nn.Module):
+    """net_2d: a module mapping {'image': (b*nv,3,h,w)} to {'feature': (b*nv,c,h,w)}; net_2d_ckpt_path: a checkpoint
+    whose 'model' entry is loaded into it (or a false value); net_3d: a module taking {'points', 'feature'}
+    (PN2SSG); feat_aggr_kwargs: the arguments of FeatureAggregation."""
+
+    def __init__(self, net_2d, net_2d_ckpt_path, net_3d, **feat_aggr_kwargs):
+        super(MVPNet3D, self).__init__()
+        if net_2d_ckpt_path:
+            _load_encoder_weights(net_2d, net_2d_ckpt_path)
+        # registration order (net_2d, feat_aggreg, net_3d) fixes the order of the state-dict keys
+        self.net_2d = net_2d
+        self.feat_aggreg = FeatureAggregation(**feat_aggr_kwargs)
+        self.net_3d = net_3d
+
+    def forward(self, data_batch):
+        """images (b,nv,3,h,w), image_xyz (b,nv,h,w,3), knn_indices (b,np,k) int64 flat pixel indices
+        view*h*w + row*w + col, points (b,3,np) -> the 3D network's predictions."""
+        images = data_batch['images']
+        b, nv, _, h, w = images.size()
+        feature_2d = self.net_2d({'image': images.reshape([-1] + list(images.shape[2:]))})['feature']
+        knn_indices = data_batch['knn_indices']
+        feature_2d = feature_2d.reshape(b, nv, -1, h, w).transpose(1, 2).contiguous().reshape(b, -1, nv * h * w)
+        feature_2d = ops.group_points(feature_2d, knn_indices)                     # (b, c, np, k)
+        with torch.no_grad():
+            image_xyz = data_batch['image_xyz'].permute(0, 4, 1, 2, 3).reshape(b, 3, nv * h * w)
+            image_xyz = ops.group_points(image_xyz, knn_indices)                   # (b, 3, np, k)
+        points = data_batch['points']
+        feature_2d3d = self.feat_aggreg(image_xyz, points, feature_2d)             # (b, out, np)
+        return self.net_3d({'points': points, 'feature': feature_2d3d})
+
+    def get_loss(self, cfg):
+        from mvpnet.models.loss import SegLoss
+        weights = None
+        if cfg.TRAIN.LABEL_WEIGHTS_PATH:
+            weights = torch.from_numpy(np.loadtxt(cfg.TRAIN.LABEL_WEIGHTS_PATH, dtype=np.float32)).cuda()
+        return SegLoss(weight=weights)
+
+    def get_metric(self, cfg):
+        from mvpnet.models.metric import SegAccuracy, SegIoU
+        make = lambda: [SegAccuracy(), SegIoU(self.net_3d.num_classes)]
+        return make(), make()

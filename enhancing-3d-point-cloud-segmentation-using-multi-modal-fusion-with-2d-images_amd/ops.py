@@ -2188,6 +2188,137 @@ def group_points(points, index):
 
 
 # --------------------------------------------------------------------------------------------
+# MVPNet baseline: the PointNet++ point ops (csrc/pn2.hip), float32 and float64
+# --------------------------------------------------------------------------------------------
+
+def _pn2_float(name, *ts):
+    """Contiguous detached operands of one floating dtype (the reference dispatches float and double)."""
+    _dev(*ts)
+    dt = ts[0].dtype
+    if dt not in (torch.float32, torch.float64) or any(t.dtype != dt for t in ts):
+        raise RuntimeError("%s: operands must all be float32 or all be float64" % name)
+    return [t.detach().contiguous() for t in ts], dt == torch.float64
+
+
+def fps(points, num_centroids):
+    """Farthest point sampling: points (B,N,D) with D in {2,3} -> int64 (B,num_centroids), the reference's picks
+    including its order among ties (mvpnet/ops/cuda/fps_kernel.cu:60-135)."""
+    (pts,), f64 = _pn2_float("fps", points)
+    if pts.dim() != 3:
+        raise RuntimeError("fps: expected points (B,N,D)")
+    B, N, D = pts.shape
+    M = int(num_centroids)
+    out = torch.empty((B, M if M > 0 else 0), device=pts.device, dtype=torch.int64)
+    nbytes = lib().mvk_fps_workspace(B, N, int(f64))
+    ws = torch.empty((nbytes,), device=pts.device, dtype=torch.uint8) if nbytes > 0 else None
+    fn = lib().mvk_fps_f64 if f64 else lib().mvk_fps
+    check(fn(_p(pts), B, N, D, M, _p(out), _p(ws), nbytes, _stream()))
+    return out
+
+
+def pn2_ball_query(query, key, radius, max_neighbors, with_distance=False):
+    """query (B,N1,3), key (B,N2,3) -> int64 (B,N1,K): the first K keys in index order with d2 < radius^2, padded with
+    the first hit, -1 where there is none (ball_query_kernel.cu:59-135). with_distance: also d2 (B,N1,K), -1 in padded
+    slots (ball_query_distance_kernel.cu)."""
+    (q, k), f64 = _pn2_float("pn2_ball_query", query, key)
+    if q.dim() != 3 or k.dim() != 3 or q.shape[2] != 3 or k.shape[2] != 3 or q.shape[0] != k.shape[0]:
+        raise RuntimeError("pn2_ball_query: expected query (B,N1,3) and key (B,N2,3)")
+    B, N1, _ = q.shape
+    N2, K = k.shape[1], int(max_neighbors)
+    index = torch.empty((B, N1, max(K, 0)), device=q.device, dtype=torch.int64)
+    dist = torch.empty((B, N1, max(K, 0)), device=q.device, dtype=q.dtype) if with_distance else None
+    fn = lib().mvk_pn2_ball_query_f64 if f64 else lib().mvk_pn2_ball_query
+    check(fn(_p(q), _p(k), B, N1, N2, float(radius), K, _p(index), _p(dist), _stream()))
+    return (index, dist) if with_distance else index
+
+
+def knn_distance(query, key, k=3):
+    """query (B,N1,3), key (B,N2,3) -> int64 index (B,N1,3) and SQUARED distance (B,N1,3) in the input dtype, ascending,
+    ties to the lower key index (knn_distance_kernel.cu:35-124). Only k = 3, like the reference."""
+    (q, ky), f64 = _pn2_float("knn_distance", query, key)
+    if q.dim() != 3 or ky.dim() != 3 or q.shape[2] != 3 or ky.shape[2] != 3 or q.shape[0] != ky.shape[0]:
+        raise RuntimeError("knn_distance: expected query (B,N1,3) and key (B,N2,3)")
+    B, N1, _ = q.shape
+    N2 = ky.shape[1]
+    index = torch.empty((B, N1, 3), device=q.device, dtype=torch.int64)
+    dist = torch.empty((B, N1, 3), device=q.device, dtype=q.dtype)
+    fn = lib().mvk_knn_distance_f64 if f64 else lib().mvk_knn_distance
+    check(fn(_p(q), _p(ky), B, N1, N2, int(k), _p(index), _p(dist), _stream()))
+    return index, dist
+
+
+_PN2_STATUS = {}
+_PN2_EAGER_CHECK = [os.environ.get("MVK_PN2_CHECK", "0") == "1"]
+
+
+def pn2_index_status(device):
+    """The int32 status word (on `device`) that the interpolation kernels set to 1 when they meet an index outside the
+    key set (such an index contributes nothing). One word per device, allocated on first use."""
+    device = torch.device(device)
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    if key not in _PN2_STATUS:
+        _PN2_STATUS[key] = torch.zeros((1,), device=device, dtype=torch.int32)
+    return _PN2_STATUS[key]
+
+
+def pn2_check_indices(device=None):
+    """Read the status word back (this waits for the device), clear it, and raise when an interpolation since the last
+    check met an index outside its key set. Call it where a wait is affordable (end of an epoch, a test); with
+    set_pn2_index_check(True) or MVK_PN2_CHECK=1 every feature_interpolate forward calls it itself."""
+    status = pn2_index_status(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
+    bad = int(status.item())
+    status.zero_()
+    if bad:
+        raise RuntimeError("feature_interpolate: an index lies outside the key set [0, N1)")
+
+
+def set_pn2_index_check(flag):
+    """True: every feature_interpolate forward waits for its status word and raises at once (one device-to-host read per
+    call, not capturable in a graph). False (default): the word is only set; pn2_check_indices() reads it."""
+    _PN2_EAGER_CHECK[0] = bool(flag)
+
+
+class _FeatureInterpolateFn(torch.autograd.Function):
+    """mvpnet/ops/interpolate.py:5-20. The backward is a float-atomic scatter-add: outside set_deterministic."""
+
+    @staticmethod
+    def forward(ctx, feature, index, weight):
+        (f, w), f64 = _pn2_float("feature_interpolate", feature, weight)
+        _dev(index)
+        if index.dtype != torch.int64:
+            raise RuntimeError("feature_interpolate: index must be int64")
+        if f.dim() != 3 or index.dim() != 3 or index.shape[2] != 3 or tuple(w.shape) != tuple(index.shape) \
+                or index.shape[0] != f.shape[0]:
+            raise RuntimeError("feature_interpolate: expected feature (B,C,N1), index (B,N2,3) and weight (B,N2,3)")
+        index = index.contiguous()
+        B, Cc, N1 = f.shape
+        N2 = index.shape[1]
+        out = torch.empty((B, Cc, N2), device=f.device, dtype=f.dtype)
+        fn = lib().mvk_interpolate_fwd_f64 if f64 else lib().mvk_interpolate_fwd
+        check(fn(_p(f), _p(index), _p(w), B, Cc, N1, N2, _p(out), _p(pn2_index_status(f.device)), _stream()))
+        if _PN2_EAGER_CHECK[0]:
+            pn2_check_indices(f.device)
+        ctx.save_for_backward(index, w)
+        ctx.n1, ctx.f64 = N1, f64
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        index, w = ctx.saved_tensors
+        g = grad_out.to(w.dtype).contiguous()
+        B, Cc, N2 = g.shape
+        gi = torch.zeros((B, Cc, ctx.n1), device=g.device, dtype=g.dtype)
+        fn = lib().mvk_interpolate_bwd_f64 if ctx.f64 else lib().mvk_interpolate_bwd
+        check(fn(_p(g), _p(index), _p(w), B, Cc, ctx.n1, N2, _p(gi), _p(pn2_index_status(g.device)), _stream()))
+        return gi, None, None
+
+
+def feature_interpolate(feature, index, weight):
+    """feature (B,C,N1), index (B,N2,3) int64, weight (B,N2,3) -> (B,C,N2) (mvpnet/ops/interpolate.py:23-35)."""
+    return _FeatureInterpolateFn.apply(feature, index, weight)
+
+
+# --------------------------------------------------------------------------------------------
 # fused FeatureAggregation path: gather kernel + MFMA linear layers
 # --------------------------------------------------------------------------------------------
 

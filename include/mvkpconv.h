@@ -669,6 +669,52 @@ int mvk_vote_predict(const double* votes, int64_t Nc, int C, const void* proj, i
 int mvk_affine_lrelu(const float* x, const float* scale, const float* shift, const float* addend, int64_t R, int C,
                      float slope, float* y, void* stream);
 
+/* ---------------- MVPNet baseline: PointNet++ point ops (csrc/pn2.hip) ------------------------- */
+/* Every entry point has a float32 and a float64 (_f64) form, like the reference's AT_DISPATCH_FLOATING_TYPES. Batched
+ * operands are contiguous rows, indices are int64. Squared distances are formed in the input dtype as
+ * ((dx*dx) + (dy*dy)) + (dz*dz), every operation rounded (no FMA). Entry points enqueue on `stream`, keep no state, and
+ * the caller owns outputs and workspaces. */
+
+/* Farthest point sampling (mvpnet/ops/cuda/fps_kernel.cu:60-135): points [B,N,D] with D in {2,3} -> index [B,M].
+ * Centroid 0 is point 0; the running distance of a point is the minimum over the chosen centroids; the next centroid is
+ * the point of largest running distance; a point at distance 0 never wins, and when no point has a positive distance
+ * the current index is repeated. Ties are broken as the reference's strided scan and LDS tree break them: with
+ * Bk = min(512, 2^floor(log2 N)) (16 below 16 points), the smallest bitreverse(j mod Bk, log2 Bk) wins, then the
+ * smallest j. 1 <= M <= N < 2^23. One workgroup per cloud. Clouds of more points than fit in registers (16 384 in
+ * float32, 8 192 in float64) keep their running distances in `workspace` (mvk_fps_workspace bytes, 0 for smaller
+ * clouds; contents need no initialisation); the picks are the same. */
+int64_t mvk_fps_workspace(int64_t B, int64_t N, int f64);
+int mvk_fps(const float* points, int B, int64_t N, int D, int64_t M, int64_t* index, void* workspace,
+            int64_t workspace_bytes, void* stream);
+int mvk_fps_f64(const double* points, int B, int64_t N, int D, int64_t M, int64_t* index, void* workspace,
+                int64_t workspace_bytes, void* stream);
+/* Ball query (ball_query_kernel.cu:59-135, ball_query_distance_kernel.cu:59-137): query [B,N1,3], key [B,N2,3] ->
+ * index [B,N1,K]: the first K keys in ascending key index with d2 < r*r, r = (dtype)radius; the remaining slots repeat
+ * the first hit; a query without a hit gets -1 in every slot. distance [B,N1,K] or NULL: d2 of the hits, -1 in the
+ * slots that were filled. Every slot of both outputs is written. */
+int mvk_pn2_ball_query(const float* query, const float* key, int B, int64_t N1, int64_t N2, float radius, int K,
+                       int64_t* index, float* distance, void* stream);
+int mvk_pn2_ball_query_f64(const double* query, const double* key, int B, int64_t N1, int64_t N2, float radius, int K,
+                           int64_t* index, double* distance, void* stream);
+/* 3-NN (knn_distance_kernel.cu:35-124): k must be 3 and N2 >= 3. index [B,N1,3] and SQUARED distance [B,N1,3] in the
+ * input dtype, ascending by distance; of two keys at the same distance the lower index comes first. */
+int mvk_knn_distance(const float* query, const float* key, int B, int64_t N1, int64_t N2, int k, int64_t* index,
+                     float* distance, void* stream);
+int mvk_knn_distance_f64(const double* query, const double* key, int B, int64_t N1, int64_t N2, int k, int64_t* index,
+                         double* distance, void* stream);
+/* Feature interpolation (interpolate_kernel.cu:25-68, :131-174): feature [B,C,N1], index [B,N2,3], weight [B,N2,3] ->
+ * out[b,c,n] = sum_k feature[b,c,index[b,n,k]] * weight[b,n,k], accumulated k = 0, 1, 2. Backward: grad_in [B,C,N1]
+ * (zero-initialised by the caller) += scatter of grad_out [B,C,N2] * weight, with float atomics (the order of the sum
+ * is not fixed). An index outside [0, N1) contributes nothing and sets *status (int32 on the device, or NULL) to 1. */
+int mvk_interpolate_fwd(const float* feature, const int64_t* index, const float* weight, int B, int C, int64_t N1,
+                        int64_t N2, float* out, int32_t* status, void* stream);
+int mvk_interpolate_fwd_f64(const double* feature, const int64_t* index, const double* weight, int B, int C, int64_t N1,
+                            int64_t N2, double* out, int32_t* status, void* stream);
+int mvk_interpolate_bwd(const float* grad_out, const int64_t* index, const float* weight, int B, int C, int64_t N1,
+                        int64_t N2, float* grad_in, int32_t* status, void* stream);
+int mvk_interpolate_bwd_f64(const double* grad_out, const int64_t* index, const double* weight, int B, int C, int64_t N1,
+                            int64_t N2, double* grad_in, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
