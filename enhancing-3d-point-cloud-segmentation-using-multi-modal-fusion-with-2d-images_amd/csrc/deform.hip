@@ -17,8 +17,6 @@
 //         power * ( 2 * mean_{n,k} min_d2 / ext^2  +  sum_i mean_n sum_{j != i} clamp_max(|loc_i - sg(loc_j)| - R, 0)^2 / K )
 //     with loc = deformed_KP / ext. One lane per point evaluates the 15 x 14 pairs, the launch also writes both
 //     gradients (they do not depend on anything upstream), so the ~50 tensor ops per layer become one launch.
-#include <stdlib.h>
-
 #include "common.h"
 
 #define DKMAX 16
@@ -566,8 +564,7 @@ extern "C" int mvk_kpconv_deform_doff(const float* q, int64_t Nq, const float* s
   P.g_min_d2 = g_min_d2; P.min_arg = min_arg; P.d_offsets = d_offsets; P.Nq = Nq; P.Ns = Ns; P.H = H; P.Cin = Cin; P.K = K;
   P.extent = extent; P.influence = influence;
   const int Cin4 = (Cin + 3) & ~3;
-  static const bool mfma_on = getenv("MVK_DOFF_MFMA") == nullptr || atoi(getenv("MVK_DOFF_MFMA")) != 0;
-  if (mfma_on && (Cin & 3) == 0) {
+  if ((Cin & 3) == 0) {
     const int chunks = (H + 63) / 64;
     const int list_cap = ((chunks + 3) / 4) * 64 > 64 ? ((chunks + 3) / 4) * 64 : 64;      // columns one wave walks
     const size_t lds = sizeof(int) * 4 * (size_t)list_cap + sizeof(float) * 4 * 48 + sizeof(float4) * 16;
@@ -576,11 +573,10 @@ extern "C" int mvk_kpconv_deform_doff(const float* q, int64_t Nq, const float* s
     MVK_CHECK_HIP(hipGetLastError());
     return 0;
   }
-  static const bool split_on = getenv("MVK_DOFF_SPLIT") == nullptr || atoi(getenv("MVK_DOFF_SPLIT")) != 0;
   // four waves per point only where points are few (the coarse levels searched at the deform radius: 750 / 160 / 36
   // points x 420 / 349 / 124 columns): with thousands of points the chip is full anyway and the per-wave overhead
   // (kernel points, the 45-value reductions) costs more than the shorter chains save (4 000 x 200: 59 -> 183 us)
-  const int wpb = (split_on && H > 64 && Nq <= 1024) ? 4 : 1;
+  const int wpb = (H > 64 && Nq <= 1024) ? 4 : 1;
   const int chunks = (H + 63) / 64;
   const int list_cap = ((chunks + wpb - 1) / wpb) * 64 > 64 ? ((chunks + wpb - 1) / wpb) * 64 : 64;   // columns one wave walks
   const size_t lds = sizeof(float) * (size_t)DKMAX * Cin4 + sizeof(int) * (size_t)wpb * list_cap + sizeof(float) * wpb * 48;

@@ -39,7 +39,6 @@ struct KPParams {
   int H, Cin, K;
   float extent;
   int influence, aggregation;
-  int zero_skip;         // gather: neighbours without any influence become shadow entries (development switch MVK_GATHER_ZEROSKIP)
   const int32_t* order;  // vector gather (rigid): work list -- the wave working on slots w .. w+PPW-1 takes the points order[w ..] (a
                          // spatially sorted permutation of 0 .. Nq-1); results land in the points' own rows. null: slot = point
   int xcd_blocks;        // with `order`: the first xcd_blocks workgroups are dealt to the 8 XCDs as 8 contiguous runs of the work list
@@ -433,7 +432,7 @@ constexpr int GWPB = 4;
 
 
 // 4 consecutive channels of a feature row / of the aggregate
-typedef float f4v __attribute__((ext_vector_type(4)));        // accumulator quad (a native vector: usable as an asm operand)
+typedef float f4v __attribute__((ext_vector_type(4)));        // accumulator quad
 __device__ __forceinline__ float4 as_float4(f4v v) { return make_float4(v.x, v.y, v.z, v.w); }
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -449,35 +448,14 @@ __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<floa
 // aggregates (LDS, fixed order -> deterministic) and writes A / min_d2 / min_arg.
 constexpr int DPPW = 16;      // most points per wave of the deformable variant
 
-//
-// FUB > 0 (rows of >= 4 elements, feature table < 4 GB, FUB = rows per batch): phase B carries no branches at
-// all, so that a whole batch of feature rows is in flight behind counted waits: the neighbour rows of a batch
-// are read from LDS together, shadow entries load row 0 and multiply it by their zero weights, the weight rows
-// of a point are padded to a multiple of FUB with zero rows, addresses are 32-bit offsets from the table base,
-// and the lane holding the ragged last quad of a row works on the row's LAST four channels instead (it
-// recomputes up to three channels of its left neighbour, bit for bit, and stores them again).
-//
-// TAIL > 0 (with FUB; rows of 4 LPP + TAIL channels, TAIL = 1..3, LPP >= 15: Cin = 66 of the early-fusion net's
-// first layer): the LPP lanes of a point take the 4 LPP leading channels as whole quads; the TAIL trailing channels
-// x 15 kernel points are spread over the same lanes -- lane l < 15 keeps kernel point l's TAIL sums and adds, per
-// neighbour, ITS weight (one ds_read_b32 of the row) times the row's TAIL trailing values (the same address for the
-// whole group). A 17th lane per point for two channels would cost a quarter of the launch (3 points per wave, not 4).
-template <int NCH, bool IDX64, bool FAST, bool DEFORM = false, int FUB = 0, int TAIL = 0>
-__global__ __launch_bounds__(64 * GWPB, NCH == 1 ? 4 : 2) void kpconv_gather_vec(KPParams P, int LPP, int PPW, int HC,
-                                                                                  int SW, int B1) {
-  constexpr bool FASTLD = FUB > 0;
-  static_assert(TAIL == 0 || (FASTLD && NCH == 1 && !DEFORM), "trailing channels: branch-free rigid variant only");
-  constexpr int TL = TAIL > 0 ? TAIL : 1;
-  // Sharing workgroups (all of them when DEFORM; with SW > 1 those from block B1 on): the waves of the workgroup
-  // share the same PPW points and take every nwv-th neighbour chunk; wave 0 adds the partial aggregates through
-  // LDS in a fixed order and stores them. A wave lives for tens of microseconds, so a launch of 1.2 rounds of
-  // independent waves takes two rounds; its last 0.2 round runs as sharing workgroups instead, four times as many
-  // waves of a quarter of the length, which fill the chip.
+template <int NCH, bool IDX64, bool FAST, bool DEFORM = false>
+__global__ __launch_bounds__(64 * GWPB, NCH == 1 ? 4 : 2) void kpconv_gather_vec(KPParams P, int LPP, int PPW, int HC) {
+  // DEFORM: the nwv waves of the workgroup share the same PPW points and take every nwv-th neighbour chunk; wave 0
+  // adds the partial aggregates through LDS in a fixed order and stores them.
   const int nwv = blockDim.x >> 6;
-  const bool share = DEFORM || (FASTLD && SW > 1 && (int)blockIdx.x >= B1);
   const float* __restrict__ X = P.x;      // features [Ns,Cin]
   float* __restrict__ Aout = P.A;         // aggregate [Nq,K,Cin]
-  constexpr int UB = FASTLD ? FUB : (NCH == 1 ? 6 : 4);  // feature rows in flight per lane
+  constexpr int UB = NCH == 1 ? 6 : 4;    // feature rows in flight per lane
   __shared__ __align__(16) float wl_all[GWPB][64 * 16 + 64 * 4];
   __shared__ float d2_all[DEFORM ? GWPB : 1][DEFORM ? 64 * 16 + DPPW * 16 : 1];  // squared distances of the chunk (rows skewed by point)
   __shared__ float4 kd[DEFORM ? DPPW * 16 : 1];                                 // deformed kernel points per point
@@ -493,8 +471,8 @@ __global__ __launch_bounds__(64 * GWPB, NCH == 1 ? 4 : 2) void kpconv_gather_vec
     const int xq = P.xcd_blocks >> 3, xr = P.xcd_blocks & 7, xc = blockIdx.x & 7;
     blk = (int64_t)xc * xq + min(xc, xr) + (blockIdx.x >> 3);
   }
-  const int64_t n0 = share ? ((int64_t)B1 * GWPB + ((int64_t)blockIdx.x - B1)) * PPW : (blk * GWPB + wid) * PPW;
-  const int hbeg = share ? wid * HC : 0, hstep = share ? nwv * HC : HC;        // this wave's neighbour chunks
+  const int64_t n0 = DEFORM ? (int64_t)blockIdx.x * PPW : (blk * GWPB + wid) * PPW;
+  const int hbeg = DEFORM ? wid * HC : 0, hstep = DEFORM ? nwv * HC : HC;        // this wave's neighbour chunks
   // phase-A identity: (point pa, neighbour slot ha)
   const int pa = lane / HC, ha = lane - pa * HC;
   const bool a_on = pa < PPW && n0 + pa < P.Nq;
@@ -506,38 +484,12 @@ __global__ __launch_bounds__(64 * GWPB, NCH == 1 ? 4 : 2) void kpconv_gather_vec
     qy = qp[1];
     qz = qp[2];
   }
-  const int HCP = FASTLD ? (HC + UB - 1) / UB * UB : HC;        // weight rows per point in LDS
-  float* wrow_a = wl + (pa * HCP + ha) * 16 + pa * 4;
+  float* wrow_a = wl + (pa * HC + ha) * 16 + pa * 4;
   // phase-B identity: (point pb, channel quad cl)
   const int pb = lane / LPP, cl = lane - pb * LPP;
   const int64_t nslot = n0 + pb;
   const bool b_on = pb < PPW && nslot < P.Nq;
-  const float* wblk_b = wl + (FASTLD ? min(pb, PPW - 1) : pb) * (HCP * 16 + 4);
-  if (FASTLD && HCP > HC) {      // padding rows: zero weights, shadow index
-    const int npad = HCP - HC;
-    if (lane < PPW * npad) {
-      const int pp = lane / npad, r = HC + lane % npad;
-      float4* dst = reinterpret_cast<float4*>(wl + (pp * HCP + r) * 16 + pp * 4);
-      dst[0] = dst[1] = dst[2] = make_float4(0.f, 0.f, 0.f, 0.f);
-      dst[3] = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
-    }
-  }
-  uint32_t c4e[NCH];      // FASTLD: first channel of the lane's quad (the ragged quad moved left to end at Cin)
-  bool c_on[NCH];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int c4 = (cl + c * LPP) * 4;
-    c_on[c] = c4 < P.Cin;
-    c4e[c] = c_on[c] ? (uint32_t)min(c4, P.Cin - 4) : 0u;
-  }
-  const uint32_t row_bytes = (uint32_t)P.Cin * 4u;
-  uint64_t batch_mask0 = 0;     // phase-A lanes of the columns 0 .. UB-1 of every point (shifted by the batch's first column)
-  for (int pp = 0; pp < PPW; ++pp) batch_mask0 |= ((1ull << UB) - 1ull) << (pp * HC);
-  const uint32_t tail_bytes = (uint32_t)(P.Cin - TAIL) * 4u;   // TAIL: offset of the trailing channels
-  const bool t_on = cl < KMAX - 1;                                               // TAIL: this lane keeps kernel point cl
-  float acc_t[TL];
-#pragma unroll
-  for (int t = 0; t < TL; ++t) acc_t[t] = 0.f;
+  const float* wblk_b = wl + pb * (HC * 16 + 4);
   const float inv_ext = 1.0f / P.extent;
   const float* __restrict__ kp = P.kp;
   const float ext2 = P.extent * P.extent;
@@ -656,13 +608,6 @@ __global__ __launch_bounds__(64 * GWPB, NCH == 1 ? 4 : 2) void kpconv_gather_vec
         for (int kk = 0; kk < KMAX - 1; ++kk)
           if (kk != bk) wv[kk] = 0.f;
       }
-      if (FASTLD && P.zero_skip) {     // no kernel point has any influence on this neighbour: a shadow entry (no row of its own is loaded,
-                        // and batches of such entries are skipped as a whole)
-        float wany = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < KMAX - 1; ++kk) wany = fmaxf(wany, fabsf(wv[kk]));
-        if (wany == 0.f) jrow = -1;
-      }
     }
     wv[15] = __int_as_float(jrow);
     {
@@ -693,36 +638,9 @@ __global__ __launch_bounds__(64 * GWPB, NCH == 1 ? 4 : 2) void kpconv_gather_vec
     // ---------------- phase B: UB feature rows in flight, then their FMAs
     const uint64_t live = __ballot(jrow >= 0);        // bit = phase-A lane (point pa, column ha) holds a real neighbour
     if (live != 0ull) {
-      for (int hb = 0; hb < HCP; hb += UB) {
-        // FASTLD: a batch whose columns are shadow entries for every point of the wave (the tail of the sorted
-        // neighbour rows: H is the 90th-percentile width, the mean row holds 3/4 of it) is skipped as a whole
-        // (only in the instantiations where the extra branch leaves the register allocation alone: with 5-row
-        // batches or three trailing channels it costs 30 spilled registers and up to a third of the speed)
-        constexpr bool SKIP = FASTLD && NCH == 1 &&
-                              (FUB == 6 || FUB == 7 || FUB == 8 || (FUB == 4 && (TAIL == 1 || TAIL == 2)));
-        if (SKIP && (live & (batch_mask0 << hb)) == 0ull) continue;
+      for (int hb = 0; hb < HC; hb += UB) {
         int jj[UB];
         float4 xv[UB][NCH];
-        float xt[UB][TL];
-        if (FASTLD) {
-#pragma unroll
-          for (int u = 0; u < UB; ++u) jj[u] = __float_as_int(wblk_b[(hb + u) * 16 + 15]);
-#pragma unroll
-          for (int u = 0; u < UB; ++u) {
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {   // byte offset < 2^32, row index and row bytes < 2^24 (checked by the host)
-              const uint32_t off = __umul24((uint32_t)max(jj[u], 0), row_bytes) + c4e[c] * 4u;
-              xv[u][c] = ld4(reinterpret_cast<const float*>(reinterpret_cast<const char*>(X) + off));
-            }
-            if (TAIL > 0) {
-              const float* pt = reinterpret_cast<const float*>(reinterpret_cast<const char*>(X) +
-                                                         (__umul24((uint32_t)max(jj[u], 0), row_bytes) + tail_bytes));
-#pragma unroll
-              for (int t = 0; t < TL; ++t) xt[u][t] = (float)pt[t];
-            }
-            asm volatile("" ::: "memory");    // loads leave in entry order, so that entry u waits for u + 1 loads only
-          }
-        } else
 #pragma unroll
         for (int u = 0; u < UB; ++u) {
           jj[u] = (hb + u < HC && b_on) ? __float_as_int(wblk_b[(hb + u) * 16 + 15]) : -2;
@@ -745,7 +663,7 @@ __global__ __launch_bounds__(64 * GWPB, NCH == 1 ? 4 : 2) void kpconv_gather_vec
         }
 #pragma unroll
         for (int u = 0; u < UB; ++u) {
-          if (FASTLD || jj[u] >= 0) {
+          if (jj[u] >= 0) {
             const float4* w4 = reinterpret_cast<const float4*>(wblk_b + (hb + u) * 16);
             const float4 wa = w4[0], wb = w4[1], wc = w4[2], wd = w4[3];
             const float wk[15] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w,
@@ -760,22 +678,6 @@ __global__ __launch_bounds__(64 * GWPB, NCH == 1 ? 4 : 2) void kpconv_gather_vec
                 acc[c][kk].w += wk[kk] * xv[u][c].w;
               }
             }
-            if (TAIL > 0) {
-              const float wraw = wblk_b[(hb + u) * 16 + (t_on ? cl : 0)];
-              const float wt = t_on ? wraw : 0.f;
-#pragma unroll
-              for (int t = 0; t < TL; ++t) acc_t[t] += wt * xt[u][t];
-            }
-            if (FASTLD) {   // entry u's products stay together: otherwise every entry's weight row is live at once
-#pragma unroll
-              for (int c = 0; c < NCH; ++c)
-#pragma unroll
-                for (int kk = 0; kk < KMAX - 1; ++kk) asm volatile("" : "+v"(acc[c][kk]));
-              if (TAIL > 0) {
-#pragma unroll
-                for (int t = 0; t < TL; ++t) asm volatile("" : "+v"(acc_t[t]));
-              }
-            }
           }
         }
       }
@@ -787,7 +689,7 @@ __global__ __launch_bounds__(64 * GWPB, NCH == 1 ? 4 : 2) void kpconv_gather_vec
     sy = ty;
     sz = tz;
   }
-  if (share) {
+  if (DEFORM) {
     // partial aggregates of waves 1..nwv-1 -> wave 0, five kernel points per round through the waves' weight rows
     __syncthreads();
     float4* mine = reinterpret_cast<float4*>(wl_all[wid]);        // [5][64] float4 = the wave's 1280 floats
@@ -815,19 +717,6 @@ __global__ __launch_bounds__(64 * GWPB, NCH == 1 ? 4 : 2) void kpconv_gather_vec
         }
         __syncthreads();
       }
-    }
-    if (TAIL > 0) {       // the trailing channels' sums, one more round
-      if (wid > 0) mine[lane] = make_float4(acc_t[0], TL > 1 ? acc_t[TL > 1 ? 1 : 0] : 0.f, TL > 2 ? acc_t[TL > 2 ? 2 : 0] : 0.f, 0.f);
-      __syncthreads();
-      if (wid == 0) {
-        for (int w = 1; w < nwv; ++w) {
-          const float4 v = reinterpret_cast<const float4*>(wl_all[w])[lane];
-          acc_t[0] += v.x;
-          if (TL > 1) acc_t[TL > 1 ? 1 : 0] += v.y;
-          if (TL > 2) acc_t[TL > 2 ? 2 : 0] += v.z;
-        }
-      }
-      __syncthreads();
     }
   }
   if (DEFORM) {
@@ -864,18 +753,18 @@ __global__ __launch_bounds__(64 * GWPB, NCH == 1 ? 4 : 2) void kpconv_gather_vec
       }
     }
   }
-  if (b_on && (!share || wid == 0)) {
+  if (b_on && (!DEFORM || wid == 0)) {
     const int64_t n = ord ? (int64_t)ord[nslot] : nslot;      // the row of this lane's phase-B identity
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-      const int c4 = FASTLD ? (int)c4e[c] : (cl + c * LPP) * 4;
-      if (FASTLD ? c_on[c] : c4 < P.Cin) {
+      const int c4 = (cl + c * LPP) * 4;
+      if (c4 < P.Cin) {
 #pragma unroll
         for (int kk = 0; kk < KMAX - 1; ++kk) {
           if (kk < P.K) {
             // (the f32 instantiations keep the dense [Nq,K,Cin] addressing: they sit at their register limit)
             float* o = Aout + (n * P.K + kk) * P.Cin + c4;
-            if (FASTLD || c4 + 3 < P.Cin) {
+            if (c4 + 3 < P.Cin) {
               st4(o, as_float4(acc[c][kk]));
             } else {
               o[0] = acc[c][kk].x;
@@ -886,11 +775,6 @@ __global__ __launch_bounds__(64 * GWPB, NCH == 1 ? 4 : 2) void kpconv_gather_vec
           }
         }
       }
-    }
-    if (TAIL > 0 && cl < P.K && t_on) {      // lane cl holds kernel point cl's sums over the trailing channels
-      float* o = Aout + (n * P.K + cl) * P.Cin + (P.Cin - TAIL);
-#pragma unroll
-      for (int t = 0; t < TL; ++t) o[t] = acc_t[t];
     }
   }
 }
@@ -1110,117 +994,50 @@ __global__ __launch_bounds__(256) void kpconv_gather_small(KPParams P) {
 // Launch geometry of the vector gather kernel for one layer (also exported: mvk_kpconv_gather_plan).
 struct VecPlan {
   int LPP, PPW, HC;   // lanes per point, points per wave, neighbours per chunk and point
-  int fub;            // rows per batch of the branch-free variant, 0 = the general variant
-  int tail;           // trailing channels handled beside the quads (TAIL of the kernel), 0 = none
-  int SW, B1, nw;     // sharing: waves per sharing workgroup (1 = none), first sharing workgroup, waves per workgroup
+  int nw;             // waves per workgroup
   int64_t wgs;        // workgroups
 };
 
-VecPlan plan_vec(int64_t Nq, int64_t Ns, int H, int Cin, bool fast, bool deform) {
+VecPlan plan_vec(int64_t Nq, int H, int Cin, bool deform) {
   VecPlan v{};
-  const int NCH = Cin <= 256 ? 1 : 2;
-  static const bool fastld_on = getenv("MVK_GATHER_FASTLD") == nullptr || atoi(getenv("MVK_GATHER_FASTLD")) != 0;
-  static const bool tail_on = getenv("MVK_GATHER_TAIL") == nullptr || atoi(getenv("MVK_GATHER_TAIL")) != 0;
-  const bool branch_free = fastld_on && fast && Ns < (1 << 24) && (uint64_t)Ns * (uint64_t)Cin * 4ull < (1ull << 32) - 64;
-  // first choice for rows of 4 m + t channels (m >= 15, t = 1..3): m lanes per point and the t trailing channels
-  // beside the quads -- if the resulting chunk length is a multiple of the 4-row batch; else ceil(Cin / 4) lanes
-  // (measured: 19 464 points x 66 channels 72 -> 67 us; 171 k points 484 -> 495 us -- the 4-row batches hide less
-  // latency once the feature table no longer sits in the caches: hence the row limit)
-  for (int with_tail = (tail_on && branch_free && !deform && NCH == 1 && Cin >= 60 && Cin % 4 != 0 &&
-                        Ns <= 65536) ? 1 : 0;
-       with_tail >= 0; --with_tail) {
-    const int c4 = with_tail ? Cin / 4 : (Cin + 3) / 4;
-    v.LPP = c4 < 64 ? c4 : 64;
-    v.PPW = 64 / v.LPP;
-    v.HC = 64 / v.PPW;
-    v.fub = 0;
-    v.tail = 0;
-    // rows per batch of the branch-free variant: the divisor-like batch size with the least padding of HC
-    if (branch_free && v.LPP >= 5) {
-      if (NCH == 2) {
-        v.fub = 4;
-      } else {
-        int best_pad = 1 << 30;
-        for (int ub = 8; ub >= 5; --ub) {
-          const int pad = (v.HC + ub - 1) / ub * ub - v.HC;
-          if (pad < best_pad) {
-            best_pad = pad;
-            v.fub = ub;
-          }
-        }
-      }
-    }
-    if (with_tail && v.fub > 0 && v.HC % 4 == 0) {      // batches of 4 rows: the trailing values take registers too
-      v.tail = Cin % 4;
-      v.fub = 4;
-      break;
-    }
+  const int c4 = (Cin + 3) / 4;
+  v.LPP = c4 < 64 ? c4 : 64;
+  v.PPW = 64 / v.LPP;
+  v.HC = 64 / v.PPW;
+  const int64_t groups = cdiv64(Nq, v.PPW);               // point groups
+  if (deform) {       // one workgroup per point group, its waves share the group's neighbour chunks (kernel comment)
+    const int chunks = (H + v.HC - 1) / v.HC;
+    v.nw = chunks < GWPB ? (chunks < 1 ? 1 : chunks) : GWPB;
+    v.wgs = groups;
+  } else {            // GWPB independent waves per workgroup
+    v.nw = GWPB;
+    v.wgs = cdiv64(groups, GWPB);
   }
-  // sharing workgroups (kernel comment): all of them for the deformable variant; for the branch-free rigid one
-  // the workgroups beyond the last full round of independent waves, when that remainder is well below a round
-  static const int split_env = getenv("MVK_GATHER_SPLIT") ? atoi(getenv("MVK_GATHER_SPLIT")) : -1;
-  const int chunks = (H + v.HC - 1) / v.HC;
-  const int64_t groups = cdiv64(Nq, v.PPW);               // point groups = independent waves
-  const int64_t plain_wgs = cdiv64(groups, GWPB);
-  const int64_t slots = NCH == 1 ? 1024 : 512;           // resident workgroups: 256 CUs x (4 | 2)
-  int64_t b1 = plain_wgs;                                 // first sharing workgroup
-  if (v.fub > 0 && chunks > 1 && split_env != 0) {
-    const int64_t full = plain_wgs / slots * slots;
-    const int64_t rem = groups - full * GWPB;             // groups left after the full rounds
-    if (split_env == 1) b1 = 0;
-    else if (rem > 0 && rem * 10 <= slots * GWPB * 7) b1 = full;
-  }
-  if (deform) b1 = 0;
-  const bool any_share = b1 < plain_wgs || deform;
-  v.nw = (b1 == 0 && any_share) ? (chunks < GWPB ? (chunks < 1 ? 1 : chunks) : GWPB) : GWPB;
-  v.SW = any_share ? GWPB : 1;
-  v.B1 = (int)b1;
-  v.wgs = any_share ? b1 + (groups - b1 * GWPB) : plain_wgs;
   return v;
 }
 
 template <int NCH, bool DEFORM = false>
 int launch_vec(KPParams P, int idx64, hipStream_t st) {
   const bool fast = P.influence == MVK_INFL_LINEAR && P.aggregation == MVK_AGG_SUM;
-  const VecPlan v = plan_vec(P.Nq, P.Ns, P.H, P.Cin, fast, DEFORM);
-  static const bool xcd_runs = getenv("MVK_GATHER_XCD_RUNS") == nullptr || atoi(getenv("MVK_GATHER_XCD_RUNS")) != 0;
+  const VecPlan v = plan_vec(P.Nq, P.H, P.Cin, DEFORM);
   if (DEFORM) P.order = nullptr;
-  P.xcd_blocks = (P.order != nullptr && xcd_runs) ? (int)(v.SW > 1 ? v.B1 : v.wgs) : 0;
-  const int LPP = v.LPP, PPW = v.PPW, HC = v.HC, fub = v.fub, SW = v.SW, B1 = v.B1, tail = v.tail;
+  P.xcd_blocks = P.order != nullptr ? (int)v.wgs : 0;
   dim3 grid((unsigned)v.wgs), block(64 * v.nw);
-#define LV(I64, F, L) \
-  hipLaunchKernelGGL((kpconv_gather_vec<NCH, I64, F, DEFORM, L>), grid, block, 0, st, P, LPP, PPW, HC, SW, B1)
-#define LVT(I64, T)                                                                                                   \
-  hipLaunchKernelGGL((kpconv_gather_vec<1, I64, true, false, 4, (TAIL_OK ? T : 0)>), grid, block, 0, st, P, LPP, \
-                     PPW, HC, SW, B1)
-  constexpr bool TAIL_OK = NCH == 1 && !DEFORM;
-#define LVF(I64)                                                                            \
-  if (TAIL_OK && tail == 1 && fub == 4) LVT(I64, 1);                                        \
-  else if (TAIL_OK && tail == 2 && fub == 4) LVT(I64, 2);                                   \
-  else if (TAIL_OK && tail == 3 && fub == 4) LVT(I64, 3);                                   \
-  else if (NCH == 2 && fub == 4) LV(I64, true, (NCH == 2 ? 4 : 0));                  \
-  else if (fub == 8) LV(I64, true, (NCH == 1 ? 8 : 0));                              \
-  else if (fub == 7) LV(I64, true, (NCH == 1 ? 7 : 0));                              \
-  else if (fub == 6) LV(I64, true, (NCH == 1 ? 6 : 0));                              \
-  else if (fub == 5) LV(I64, true, (NCH == 1 ? 5 : 0));                              \
-  else if (fast) LV(I64, true, 0);                                                          \
-  else LV(I64, false, 0);
+#define LV(I64, F) hipLaunchKernelGGL((kpconv_gather_vec<NCH, I64, F, DEFORM>), grid, block, 0, st, P, v.LPP, v.PPW, v.HC)
   if (idx64) {
-    LVF(true)
+    if (fast) LV(true, true);
+    else LV(true, false);
   } else {
-    LVF(false)
+    if (fast) LV(false, true);
+    else LV(false, false);
   }
-#undef LVF
-#undef LVT
 #undef LV
   return 0;
 }
 
 // channel tiles per wave of the MFMA gather for rows of Cin channels (0: the layer stays on the vector kernels)
 int mfma_tiles(int64_t Ns, int Cin, int K, int influence, int aggregation) {
-  static const bool on = getenv("MVK_GATHER_MFMA") == nullptr || atoi(getenv("MVK_GATHER_MFMA")) != 0;
-  static const int min_cin = getenv("MVK_GATHER_MFMA_MIN_CIN") ? atoi(getenv("MVK_GATHER_MFMA_MIN_CIN")) : 1;      // (5: rows of <= 4 channels stay on kpconv_gather_small)
-  if (!on || influence != MVK_INFL_LINEAR || aggregation != MVK_AGG_SUM || K > 16 || Cin < min_cin) return 0;
+  if (influence != MVK_INFL_LINEAR || aggregation != MVK_AGG_SUM || K > 16 || Cin < 1) return 0;
   if ((uint64_t)Ns * (uint64_t)Cin >= (1ull << 32) - 4096) return 0;
   if (Cin <= 32) return 2;
   if (Cin <= 64) return 4;
@@ -1236,15 +1053,12 @@ struct MfmaPlan {
 };
 MfmaPlan plan_mfma(int64_t Nq, int64_t Ns, int H, int Cin, int K, int influence, int aggregation, bool deform) {
   MfmaPlan m{};
-  static const bool mfma_deform = getenv("MVK_DEFORM_MFMA") == nullptr || atoi(getenv("MVK_DEFORM_MFMA")) != 0;
-  if (deform && !mfma_deform) return m;
   m.T = mfma_tiles(Ns, Cin, K, influence, aggregation);
   if (m.T == 0) return m;
   // few points with long rows: the four waves of a workgroup share one point (kernel comment)
-  static const int sw_env = getenv("MVK_GATHER_MFMA_SHARE") ? atoi(getenv("MVK_GATHER_MFMA_SHARE")) : -1;
   m.blocks_y = cdiv64(Cin, 16 * m.T);
   const bool can_share = m.T >= 4 && m.T != 5;          // (instantiated for the tile counts the coarse levels use)
-  m.SW = !can_share ? 1 : (sw_env >= 0 ? (sw_env > 1 ? 4 : 1) : ((H >= 128 || (Nq * m.blocks_y <= 512 && H >= 32)) ? 4 : 1));
+  m.SW = (can_share && (H >= 128 || (Nq * m.blocks_y <= 512 && H >= 32))) ? 4 : 1;
   m.wgs = m.SW > 1 ? Nq : cdiv64(Nq, 4);
   return m;
 }
@@ -1254,10 +1068,9 @@ bool launch_mfma(KPParams P, int idx64, hipStream_t st) {
   const MfmaPlan mp = plan_mfma(P.Nq, P.Ns, P.H, P.Cin, P.K, P.influence, P.aggregation, KPM == 1);
   const int T = mp.T;
   if (T == 0) return false;
-  static const bool xcd_runs = getenv("MVK_GATHER_XCD_RUNS") == nullptr || atoi(getenv("MVK_GATHER_XCD_RUNS")) != 0;
   const int SW = mp.SW;
   const int64_t wgs = mp.wgs;
-  P.xcd_blocks = (P.order != nullptr && xcd_runs) ? (int)wgs : 0;
+  P.xcd_blocks = P.order != nullptr ? (int)wgs : 0;
   dim3 grid((unsigned)wgs, (unsigned)mp.blocks_y), block(256);
 #define LM1(TT, MD, SH)                                                                              \
   if (idx64) hipLaunchKernelGGL((kpconv_gather_mfma<TT, MD, true, KPM, SH>), grid, block, 0, st, P);     \
@@ -1281,10 +1094,8 @@ bool launch_mfma(KPParams P, int idx64, hipStream_t st) {
 template <int MODE, bool DEFORM>
 int launch_lane_channel(const KPParams& P, int idx64, hipStream_t st) {
   // scatter of a layer with more than one 64-neighbour chunk (searched at the deform radius): four waves per point
-  static const bool split_on = getenv("MVK_SCATTER_SPLIT") == nullptr || atoi(getenv("MVK_SCATTER_SPLIT")) != 0;
-  static const bool spread_on = getenv("MVK_SCATTER_SPREAD") == nullptr || atoi(getenv("MVK_SCATTER_SPREAD")) != 0;
-  const bool split = MODE == 1 && split_on && P.H > 64;
-  if (MODE == 1 && !DEFORM && !split && spread_on && P.Nq < 2048) {
+  const bool split = MODE == 1 && P.H > 64;
+  if (MODE == 1 && !DEFORM && !split && P.Nq < 2048) {
     // few points (coarse levels): one wave per (point, 64-channel slot), and below ~4 000 such waves four waves per
     // slot that take every fourth neighbour (see the kernel's HS parameter)
     const int slots = (P.Cin + 63) / 64;
@@ -1361,21 +1172,18 @@ extern "C" int mvk_kpconv_gather_fwd_ordered(const float* q, int64_t Nq, const f
   P.q = q; P.s = s; P.idx = idx; P.x = x; P.kp = kp; P.offsets = offsets; P.min_d2 = min_d2; P.min_arg = min_arg;
   P.A = A_out; P.Nq = Nq; P.Ns = Ns; P.H = H; P.Cin = Cin; P.K = K; P.extent = extent;
   P.influence = influence; P.aggregation = aggregation;
-  static const int zero_skip = getenv("MVK_GATHER_ZEROSKIP") ? atoi(getenv("MVK_GATHER_ZEROSKIP")) : 1;
-  P.zero_skip = zero_skip;
   if (H == 0) {
     MVK_CHECK_HIP(hipMemsetAsync(A_out, 0, sizeof(float) * Nq * K * Cin, st));
     if (offsets == nullptr) return 0;
   }
   if (offsets != nullptr) {
-    static const bool vec_deform = getenv("MVK_DEFORM_VEC") == nullptr || atoi(getenv("MVK_DEFORM_VEC")) != 0;
     KPParams Pm = P;
     Pm.order = nullptr;           // (the deformable levels are the coarse ones: no work list)
     if (launch_mfma<1>(Pm, idx64, st)) {
       // (round 5: the deformable forward on the matrix pipe as well, KPM 1 of kpconv_gather_mfma)
-    } else if (vec_deform && Cin >= 13 && Cin <= 256) {          // 64 / ceil(Cin/4) <= DPPW points per wave
+    } else if (Cin >= 13 && Cin <= 256) {          // 64 / ceil(Cin/4) <= DPPW points per wave
       launch_vec<1, true>(P, idx64, st);
-    } else if (vec_deform && Cin > 256 && Cin <= 512) {
+    } else if (Cin > 256 && Cin <= 512) {
       launch_vec<2, true>(P, idx64, st);
     } else {
       launch_lane_channel<0, true>(P, idx64, st);
@@ -1467,10 +1275,11 @@ extern "C" int mvk_kpconv_scatter_bwd(const float* q, int64_t Nq, const float* s
 }
 
 // Launch geometry mvk_kpconv_gather_fwd uses for a layer (elem_bytes: 4, the f32 rows -- the only row type)
-// with linear influence and sum aggregation: out[0..6] = lanes per point, points per wave, rows per batch of the
-// branch-free variant (0 = general variant), first sharing workgroup, waves per workgroup, workgroups, grid
-// threads (what a kernel trace reports). out[5] = 0: the layer runs on another kernel (one point per wave, or one
-// point per lane for rows of <= 4 channels).
+// with linear influence and sum aggregation: out[0..7] = lanes per point, points per wave, channel tiles per wave
+// (MFMA gather; 0 on the vector kernel), first sharing workgroup (0: every workgroup shares its points among its
+// waves; the workgroup count, or -1 on the MFMA gather: none does), waves per workgroup, workgroups, grid threads
+// (what a kernel trace reports), 1 = the MFMA gather. out[5] = 0: the layer runs on another kernel (one point per
+// wave, or one point per four lanes for rows of <= 4 channels).
 extern "C" int mvk_kpconv_gather_plan(int64_t Nq, int64_t Ns, int H, int Cin, int elem_bytes, int deformable,
                                       int64_t* out) {
   MVK_REQUIRE(out != nullptr && elem_bytes == 4, "kpconv plan: bad arguments (feature rows are f32: elem_bytes 4)");
@@ -1482,8 +1291,8 @@ extern "C" int mvk_kpconv_gather_plan(int64_t Nq, int64_t Ns, int H, int Cin, in
     return 0;
   }
   if (Nq <= 0 || Cin <= 0 || Cin > 512 || (deformable && Cin < 13) || (!deformable && Cin <= 4)) return 0;      // (one point per 4 lanes: kpconv_gather_small)
-  const VecPlan v = plan_vec(Nq, Ns, H, Cin, true, deformable != 0);
-  out[0] = v.LPP; out[1] = v.PPW; out[2] = v.fub; out[3] = v.B1; out[4] = v.nw; out[5] = v.wgs;
+  const VecPlan v = plan_vec(Nq, H, Cin, deformable != 0);
+  out[0] = v.LPP; out[1] = v.PPW; out[3] = deformable ? 0 : v.wgs; out[4] = v.nw; out[5] = v.wgs;
   out[6] = v.wgs * 64 * v.nw;
   return 0;
 }

@@ -184,8 +184,9 @@ def gemm_plan(M, N, Kd, split_k=None, want_stats=False):
 
 def kpconv_gather_plan(Nq, Ns, H, Cin, elem_bytes=4, deformable=False):
     """Launch geometry of the gather kernel for a (linear, sum) layer (mvk_kpconv_gather_plan): dict with the
-    lanes per point, points per wave, rows per batch, first sharing workgroup, waves per workgroup, workgroups and
-    grid threads; 'workgroups' 0 means the layer runs on the one-point-per-wave kernel."""
+    lanes per point, points per wave, 'rows_per_batch' (the MFMA gather's channel tiles per wave; 0 on the vector
+    kernel), first sharing workgroup, waves per workgroup, workgroups and grid threads; 'workgroups' 0 means the layer
+    runs on the one-point-per-wave kernel."""
     out = (C.c_int64 * 8)()
     check(lib().mvk_kpconv_gather_plan(int(Nq), int(Ns), int(H), int(Cin), int(elem_bytes), int(bool(deformable)), out))
     keys = ("lanes_per_point", "points_per_wave", "rows_per_batch", "first_sharing_workgroup", "waves_per_workgroup",
@@ -410,10 +411,8 @@ def _gather_kernel_label(Nq, Ns, H, Cin, deform, elem_bytes=4):
         return _gather_kernel_name(Cin, deform)
     if p.get("mfma"):
         return "kpconv_gather_mfma<T=%d>(1 point per wave)" % p["rows_per_batch"]
-    tail = Cin - 4 * p["lanes_per_point"] if 4 * p["lanes_per_point"] < Cin else 0
-    return "kpconv_gather_vec<NCH=%d%s>(LPP=%d,PPW=%d%s)" % (1 if Cin <= 256 else 2, ",deform" if deform else "",
-                                                             p["lanes_per_point"], p["points_per_wave"],
-                                                             ",+%d trailing channels" % tail if tail else "")
+    return "kpconv_gather_vec<NCH=%d%s>(LPP=%d,PPW=%d)" % (1 if Cin <= 256 else 2, ",deform" if deform else "",
+                                                           p["lanes_per_point"], p["points_per_wave"])
 
 
 def profile_collect(h_eff=None):

@@ -301,12 +301,20 @@ def test_kpconv_config1_literal_radius_degenerate_rows(ops, idt):
     check_err("config 1 literal r=0.04: dW", rel_err(Wt.grad.cpu().numpy(), dW), FP_TOL)
 
 
-@pytest.mark.parametrize("cin,cout,H", [(1, 5, 9), (4, 32, 17), (8, 8, 70), (20, 12, 33), (68, 64, 40),
-                                        (128, 16, 25), (256, 8, 64), (512, 4, 10), (516, 4, 6), (1040, 3, 5),
-                                        (2, 6, 130), (130, 16, 150), (600, 4, 130), (30, 5, 260),
-                                        (61, 8, 40), (62, 8, 16), (67, 8, 33), (129, 8, 20), (255, 4, 70)])
-def test_kpconv_every_kernel_variant_vs_numpy_oracle(ops, cin, cout, H):
-    """Seeded inputs through every gather / scatter template instantiation (LPP = 1..64, NCH = 1, 2,
+VARIANT_SHAPES = [(1, 5, 9), (4, 32, 17), (8, 8, 70), (20, 12, 33), (68, 64, 40),
+                  (128, 16, 25), (256, 8, 64), (512, 4, 10), (516, 4, 6), (1040, 3, 5),
+                  (2, 6, 130), (130, 16, 150), (600, 4, 130), (30, 5, 260),
+                  (61, 8, 40), (62, 8, 16), (67, 8, 33), (129, 8, 20), (255, 4, 70)]
+# (linear, sum) runs on the MFMA gather wherever it can; the other two modes keep kpconv_gather_vec (5 <= Cin <= 512)
+VARIANT_MODES = [("linear", "sum"), ("gaussian", "sum"), ("linear", "closest")]
+
+
+@pytest.mark.parametrize("cin,cout,H,influence,agg", [
+    pytest.param(*shape, *mode, id="-".join(str(v) for v in (shape if mode == VARIANT_MODES[0] else shape + mode)))
+    for mode in VARIANT_MODES for shape in VARIANT_SHAPES])
+def test_kpconv_every_kernel_variant_vs_numpy_oracle(ops, cin, cout, H, influence, agg):
+    """Seeded inputs through every gather / scatter template instantiation (LPP = 1..64, NCH = 1, 2 of the vector
+    gather under the gaussian influence and the `closest` aggregation, the MFMA gather's tile counts under linear / sum,
     the generic lane = channel kernel and its > 512-channel multi-launch path, the one-lane-per-point kernel for rows
     of <= 4 channels, the four-waves-per-point scatter of rows with more than 64 neighbour columns) against the float64
     numpy restatement; includes shadow neighbours, empty rows and a ragged last chunk."""
@@ -323,14 +331,46 @@ def test_kpconv_every_kernel_variant_vs_numpy_oracle(ops, cin, cout, H):
     W = (rng.normal(size=(K, cin, cout)) * 0.1).astype(np.float32)
     g = rng.normal(size=(Nq, cout)).astype(np.float32)
     xt, Wt = T(x).requires_grad_(True), T(W).requires_grad_(True)
-    y, _ = ops.kpconv(T(q), T(s), T(idx), xt, T(kp), Wt, 0.06)
+    y, _ = ops.kpconv(T(q), T(s), T(idx), xt, T(kp), Wt, 0.06, influence, agg)
     (y * T(g)).sum().backward()
     a64 = [a.astype(np.float64) for a in (q, s)] + [idx.astype(np.int64), x.astype(np.float64), kp.astype(np.float64),
                                                      W.astype(np.float64), 0.06]
-    assert rel_err(y.detach().cpu().numpy(), npref.kpconv_forward(*a64)) < FP_TOL
-    dx, dW = npref.kpconv_backward(*a64, g.astype(np.float64))
+    assert rel_err(y.detach().cpu().numpy(), npref.kpconv_forward(*a64, influence, agg)) < FP_TOL
+    dx, dW = npref.kpconv_backward(*a64, g.astype(np.float64), influence, agg)
     assert rel_err(xt.grad.cpu().numpy(), dx) < FP_TOL
     assert rel_err(Wt.grad.cpu().numpy(), dW) < FP_TOL
+
+
+@pytest.mark.parametrize("cin,H", [(20, 70), (61, 150), (300, 70)])
+def test_kpconv_deformable_vector_gather_closest_vs_numpy_oracle(ops, cin, H):
+    """Deformable layers with the `closest` aggregation run on kpconv_gather_vec<DEFORM> (the MFMA gather takes
+    linear / sum only): LPP 5 / 16 / 64, NCH 1 and 2, a ragged last quad (61), a last point group that is not full
+    (50 points) and more than one neighbour chunk per wave, so that the waves of a workgroup share their points.
+    Aggregate and min_d2 (over real and shadow entries) against the float64 numpy restatement; linear influence, where
+    the reference's in-range filter drops weights that are exactly zero."""
+    from oracle import npref
+    rng = np.random.default_rng(cin * 131 + H)
+    Nq, Ns, K, ext = 50, 301, 15, 0.06
+    q = (rng.random((Nq, 3)) * 0.3).astype(np.float32)
+    s = (rng.random((Ns, 3)) * 0.3).astype(np.float32)
+    idx = rng.integers(0, Ns + 1, (Nq, H)).astype(np.int32)
+    idx[:, H // 2:][rng.random((Nq, H - H // 2)) < 0.5] = Ns
+    idx[5] = Ns                                   # a row of shadow neighbours only
+    x = rng.normal(size=(Ns, cin)).astype(np.float32)
+    kp = (rng.normal(size=(K, 3)) * 0.05).astype(np.float32)
+    off = (rng.normal(size=(Nq, K, 3)) * 0.02).astype(np.float32)
+    A, min_d2 = ops.kpconv_gather(T(q), T(s), T(idx), T(x), T(kp), ext, aggregation="closest", offsets=T(off),
+                                  want_min_d2=True)
+    a64 = [a.astype(np.float64) for a in (q, s)] + [idx.astype(np.int64), x.astype(np.float64), kp.astype(np.float64)]
+    _, want, _ = npref.kpconv_forward(*a64, np.zeros((K, cin, 1)), ext, aggregation="closest",
+                                      offsets=off.astype(np.float64), return_A=True)
+    assert rel_err(A.cpu().numpy(), want) < FP_TOL
+    _, d2 = npref.kpconv_weights(a64[0], a64[1], a64[2], a64[4], ext, aggregation="closest", offsets=off.astype(np.float64))
+    want_min = d2.min(axis=1)
+    got_min = min_d2.cpu().numpy()
+    real = (idx < Ns).any(1)                      # (the all-shadow row's minima are ~3e12: compared on their own scale)
+    assert rel_err(got_min[real], want_min[real]) < FP_TOL
+    assert rel_err(got_min[~real], want_min[~real]) < FP_TOL
 
 
 @pytest.mark.parametrize("Nq,cin,H", [(40000, 32, 12), (70000, 66, 30), (17000, 64, 40), (21000, 128, 70), (19000, 66, 40),

@@ -1,7 +1,7 @@
 """Development-only: the level-0 gather with a work list (mvk_kpconv_gather_fwd_ordered) -- launch time inside a graph
 for the row order, a Morton order, the cell order the neighbour search builds and a random order; 1 and 8 spheres.
   python tools/gather_order_bench.py [cin] [pmc]     pmc: three plain launches per order, for a rocprofv3 --pmc pass
-With MVK_GATHER_SPLIT=0 (no sharing workgroups) every order must give the same bits; the tool prints the differing rows."""
+Every order must give the same bits; the tool prints the differing rows."""
 import os, sys, torch, numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

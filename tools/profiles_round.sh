@@ -46,16 +46,11 @@ python3 $R/tools/trace_steady.py $F5 5 90 > $O/${TAG}_steady_state_5spheres.txt
 rm -rf $O/k5
 cd $R && MVK_BENCH_DETAIL=$O/${TAG}_bench_detail_5spheres.json python3 bench.py --full --spheres 5 --views 5 --steps 20 --warmup 3 --no-cpu-baseline > $O/${TAG}_bench_line_5spheres.json 2> $O/b5.err; cd /tmp
 # 8. (round 4) deterministic mode against the default, gather-form feature gradient against the atomic scatter
-{ for e in X=0 MVK_DETERMINISTIC=1 MVK_REVERSE_DX=0 MVK_GATHER_MFMA=0 MVK_REV_FUSED=0 MVK_BN_FOLD=1 MVK_INPUTS_IN_GRAPH=0 MVK_BENCH_DUMMY_LAUNCHES=100; do echo -n "$e: "; env $e python3 $R/bench.py --dev --steps 30 --warmup 3 --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['ms_per_step'], 'ms/step,', d['value'], d['unit'])"; done;
+{ for e in X=0 MVK_DETERMINISTIC=1 MVK_REVERSE_DX=0 MVK_REV_FUSED=0 MVK_BN_FOLD=1 MVK_INPUTS_IN_GRAPH=0 MVK_BENCH_DUMMY_LAUNCHES=100; do echo -n "$e: "; env $e python3 $R/bench.py --dev --steps 30 --warmup 3 --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['ms_per_step'], 'ms/step,', d['value'], d['unit'])"; done;
   for e in X=0 MVK_REVERSE_DX=0; do echo -n "8 spheres, $e: "; env $e python3 $R/bench.py --spheres 8 --steps 10 --warmup 2 --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['ms_per_step'], 'ms/step,', d['value'], d['unit'])"; done; } > $O/${TAG}_modes.txt 2>&1
 # 9. (round 4) what each side branch costs the step (pieces left out of the captured step: timing only), the input kernels'
 #    one-workgroup paths against the multi-workgroup front ends, and the level-0 neighbour kernels stand-alone
 cd $R
 { for e in X=0 MVK_BENCH_SKIP=enc MVK_BENCH_SKIP=chain MVK_BENCH_SKIP=fa MVK_BENCH_SKIP=enc,chain,fa MVK_BENCH_SKIP=chain,fa MVK_BENCH_SKIP=enc,fa "MVK_SUB_MULTI_MIN=0 MVK_NB_MULTI_MIN=0" X=0; do echo -n "$e: "; env $e python3 $R/bench.py --dev --steps 30 --warmup 3 --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['ms_per_step'], 'ms/step,', d['value'], d['unit'])"; done;
   for e in X=0 MVK_BENCH_SKIP=enc MVK_BENCH_SKIP=chain MVK_BENCH_SKIP=enc,chain,fa "MVK_SUB_MULTI_MIN=0 MVK_NB_MULTI_MIN=0"; do echo -n "5 spheres x 5 views, $e: "; env $e python3 $R/bench.py --dev --spheres 5 --views 5 --steps 10 --warmup 2 --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['ms_per_step'], 'ms/step,', d['value'], d['unit'])"; done; } > $O/${TAG}_side_branches.txt 2>&1
-ls -la $O
-# 10. (round 5) operator bench of the MFMA gather against the vector kernel (the deformable configurations: tools/config_profiles.sh)
-cd $R
-MVK_GATHER_MFMA=1 python3 tools/gather_mfma_bench.py mfma > $O/${TAG}_gather_mfma_bench.txt 2>/dev/null
-MVK_GATHER_MFMA=0 python3 tools/gather_mfma_bench.py vec 2>/dev/null | grep "level" >> $O/${TAG}_gather_mfma_bench.txt
 ls -la $O
