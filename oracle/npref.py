@@ -43,15 +43,24 @@ def kpconv_weights(q, s, idx, kp, extent, influence="linear", aggregation="sum",
     return w, d2
 
 
+def deform_in_range(idx, Ns, d2, extent):
+    """keep[n,h] of the deformable branch (blocks.py:306-325): entry h stays a neighbour when it is a real one and lies
+    within `extent` of AT LEAST ONE deformed kernel point, strictly (d2 < extent**2); every other column is re-pointed
+    to the shadow row (zero features)."""
+    return (idx < Ns) & np.any(d2 < d2.dtype.type(extent) ** 2, axis=2)
+
+
 def kpconv_forward(q, s, idx, x, kp, W, extent, influence="linear", aggregation="sum",
                    offsets=None, modulations=None, return_A=False):
     """y[n,:] = sum_k (sum_h w[n,h,k] x+[idx[n,h]]) @ W[k]   (SURVEY.md A.4).
 
-    The deformable neighbour re-compaction (blocks.py:300-325) only removes
-    neighbours whose weight is exactly 0 under the linear influence, so the
-    dense formula below is the same function (checked against the reference by
-    the golden fixtures)."""
+    Rigid: the dense formula. Deformable (offsets given): the neighbour re-compaction of blocks.py:300-325 is applied
+    as a mask on the columns (deform_in_range) for EVERY influence. Under the linear influence it only removes weights
+    that are exactly 0; under the gaussian and constant influences it removes non-zero weights, so it changes A and y
+    (and, in the backward, dx, dW and d_offsets)."""
     w, d2 = kpconv_weights(q, s, idx, kp, extent, influence, aggregation, offsets)
+    if offsets is not None:
+        w = w * deform_in_range(idx, s.shape[0], d2, extent)[:, :, None]
     xp = np.concatenate([x, np.zeros((1, x.shape[1]), x.dtype)], 0)  # :357
     nx = xp[idx]                                                      # :360  [N,H,Cin]
     A = np.einsum("nhk,nhc->nkc", w, nx)                              # :363
@@ -73,6 +82,75 @@ def kpconv_backward(q, s, idx, x, kp, W, extent, g, influence="linear", aggregat
     dxp = np.zeros_like(xp)
     np.add.at(dxp, idx.reshape(-1), contrib.reshape(-1, x.shape[1]))
     return dxp[:Ns], dW
+
+
+def kpconv_deform_backward(q, s, idx, x, kp, W, extent, offsets, modulations, g_y, g_min_d2, influence="linear"):
+    """Deformable (and modulated) KPConv, sum aggregation, forward and every gradient of
+        loss = sum(y * g_y) + sum(min_d2 * g_min_d2)
+    in the dtype of the inputs (float64 for an oracle, float32 to see what the number format alone costs).
+    Algebra: header of csrc/deform.hip, SURVEY.md A.4 / A.6. With rel[n,h] = s+[idx[n,h]] - q[n] (the shadow point sits at
+    1e6), kpdef = kp + offsets, diff[n,h,k] = rel[n,h] - kpdef[n,k], d2 = |diff|^2, keep = deform_in_range and
+    w = influence(d2) * keep:
+        A[n,k,c] = sum_h w[n,h,k] x+[idx[n,h],c]        (unmodulated; Am = A * modulations)
+        y = sum_k Am[:,k,:] @ W[k]                       min_d2[n,k] = min_h d2[n,h,k]   (shadow entries included)
+        dW[k] = Am[:,k,:]^T g_y                          dAm = g_y W^T
+        d_modulations = sum_c dAm * A                    dA = dAm * modulations
+        dx[idx[n,h]] += sum_k w[n,h,k] dA[n,k,:]
+        d_offsets[n,k] = sum_h keep (dw/doff)[n,h,k] B[n,h,k]  -  2 diff[n,h*,k] g_min_d2[n,k]
+    with B[n,h,k] = sum_c x+[idx[n,h],c] dA[n,k,c], h* the arg-min column, and
+        dw/doff = diff / (extent sqrt(d2)) inside the support (linear), 2 w diff / den (gaussian), 0 (constant).
+    modulations / g_min_d2 may be None. Returns (dx, dW, d_offsets, d_modulations or None, A, y, min_d2, diag) with
+    diag = {kept [Nq] kept columns per row, keep [Nq,H], kink_band: real entries with |sqrt(d2)/extent - 1| < 1e-5,
+    argmin_ties: (n,k) whose minimum is approached within 1e-5 relative by ANOTHER support point,
+    d_offsets_min: the min_d2 term of d_offsets alone, dA: the gradient of the unmodulated aggregate}."""
+    dt = q.dtype
+    Ns, Cin = s.shape[0], x.shape[1]
+    ext = dt.type(extent)
+    sp = np.concatenate([s, np.full((1, 3), 1e6, dt)], 0)
+    rel = sp[idx] - q[:, None, :]                                     # [N,H,3]
+    kpdef = kp[None] + offsets                                        # [N,K,3]
+    diff = rel[:, :, None, :] - kpdef[:, None]                        # [N,H,K,3]
+    d2 = np.sum(diff ** 2, axis=3, dtype=dt)                          # [N,H,K]
+    hstar = np.argmin(d2, axis=1)                                     # [N,K]
+    min_d2 = np.take_along_axis(d2, hstar[:, None, :], axis=1)[:, 0]
+    real = idx < Ns
+    keep = deform_in_range(idx, Ns, d2, extent)
+    wf = kp_influence(d2, extent, influence)
+    w = wf * keep[:, :, None]
+    xp = np.concatenate([x, np.zeros((1, Cin), dt)], 0)
+    nx = xp[idx]                                                      # [N,H,Cin]
+    A = np.einsum("nhk,nhc->nkc", w, nx)
+    Am = A * modulations[:, :, None] if modulations is not None else A
+    y = np.einsum("nkc,kco->no", Am, W)
+    dW = np.einsum("nkc,no->kco", Am, g_y)
+    dAm = np.einsum("no,kco->nkc", g_y, W)
+    d_mod = None
+    dA = dAm
+    if modulations is not None:
+        d_mod = np.sum(dAm * A, axis=2, dtype=dt)
+        dA = dAm * modulations[:, :, None]
+    dxp = np.zeros_like(xp)
+    np.add.at(dxp, idx.reshape(-1), np.einsum("nhk,nkc->nhc", w, dA).reshape(-1, Cin))
+    B = np.einsum("nhc,nkc->nhk", nx, dA)
+    if influence == "linear":
+        inside = keep[:, :, None] & (wf > 0) & (d2 > 0)
+        sc = np.where(inside, 1 / (ext * np.sqrt(np.where(inside, d2, 1))), 0).astype(dt)
+    elif influence == "gaussian":
+        sc = (2 * w / dt.type(2 * (extent * 0.3) ** 2 + 1e-9)).astype(dt)
+    else:
+        sc = np.zeros_like(d2)
+    d_off = np.einsum("nhk,nhkd->nkd", sc * B, diff)
+    d_off_min = np.zeros_like(d_off)
+    if g_min_d2 is not None:
+        at_min = np.take_along_axis(diff, hstar[:, None, :, None], axis=1)[:, 0]      # [N,K,3]
+        d_off_min = -2 * at_min * g_min_d2[:, :, None]
+    # diagnostics: where the function (or its gradient) jumps
+    dist = np.sqrt(d2)
+    kink = int(np.count_nonzero(real[:, :, None] & (np.abs(dist / ext - 1) < 1e-5)))
+    other = idx[:, :, None] != np.take_along_axis(idx, hstar, axis=1)[:, None, :]   # another support point than h*'s
+    ties = int(np.count_nonzero(np.any(other & (d2 <= min_d2[:, None, :] * (1 + 1e-5)), axis=1)))
+    diag = dict(kept=keep.sum(1), keep=keep, kink_band=kink, argmin_ties=ties, d_offsets_min=d_off_min, dA=dA)
+    return dxp[:Ns], dW, (d_off + d_off_min).astype(dt), d_mod, A, y, min_d2, diag
 
 
 # ---------------------------------------------------------------------------

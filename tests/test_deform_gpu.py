@@ -1,0 +1,125 @@
+"""Deformable (and modulated) KPConv on the HIP path against the float64 oracle (oracle/npref.py:kpconv_deform_backward)
+over the case table of tests/deform_cases.py: both offset-gradient kernels of csrc/deform.hip (MFMA for Cin % 4 == 0, the
+vector kernel with one or four waves per point otherwise), the scatter and the gather form of the feature gradient,
+every forward kernel a deformable layer can reach, the three influences with the reference's in-range filter, with and
+without modulations, int32 and int64 indices. tests/test_deform_cpu.py shows that no input of the table sits where the
+function or its gradient jumps, so every element of every tensor is compared; the measured errors are logged next to
+their bounds (profiles/deform_parity_errors.txt)."""
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+import deform_cases as dc
+
+pytestmark = pytest.mark.gpu
+
+PKG = "enhancing-3d-point-cloud-segmentation-using-multi-modal-fusion-with-2d-images_amd"
+FP_TOL = 1e-4        # north_star: "within 1e-4 rel for KPConv float outputs"
+DEFORM_TOL = 1e-4    # gradients through the offset branch (tests/test_gpu_parity.py)
+
+
+@pytest.fixture(scope="module")
+def ops():
+    assert torch.cuda.is_available(), "-m gpu tests need the MI355X"
+    return importlib.import_module(PKG + ".ops")
+
+
+def T(a):
+    return None if a is None else torch.from_numpy(np.array(a)).cuda()          # (a copy: the cached inputs are read-only)
+
+
+def N(t):
+    return t.detach().cpu().numpy()
+
+
+def _zero_rows(name):
+    """Rows that keep no neighbour at all (ROW_SHADOW, ROW_FAR and whatever else the oracle finds)."""
+    rows = np.nonzero(dc.oracle64(name).diag["kept"] == 0)[0]
+    assert dc.ROW_SHADOW in rows and dc.ROW_FAR in rows
+    return rows
+
+
+SWEEP = [pytest.param(c.name, use_rev, id="%s-%s" % (c.name, "gather" if use_rev else "scatter"))
+         for c in dc.CASES for use_rev in ((False, True) if dc.dispatch(c)["gather_dx"] else (False,))]
+
+
+@pytest.mark.parametrize("name,use_rev", SWEEP)
+def test_deformable_kpconv_vs_float64_oracle(ops, name, use_rev):
+    """ops.kpconv autograd with loss = sum(y g) + sum(min_d2 gm): y, min_d2, dx, dW, d_offsets and d_modulations against the
+    oracle under the max-norm bound and the per-row bound (dc.compare). use_rev False: the feature gradient is the atomic
+    scatter launch_lane_channel<1, DEFORM>; True (linear influence): mvk_kpconv_gather_rev_deform over
+    ops.reverse_neighbors(idx, Ns). The rows that keep no neighbour give exactly zero y, and their d_offsets is the
+    min_d2 term alone."""
+    c, i, o = dc.BY_NAME[name], dc.make_inputs(name), dc.oracle64(name)
+    q, s, idx, kp = T(i.q), T(i.s), T(i.idx), T(i.kp)
+    x, W, off = T(i.x).requires_grad_(True), T(i.W).requires_grad_(True), T(i.offsets).requires_grad_(True)
+    mod = T(i.modulations).requires_grad_(True) if c.mod else None
+    rev = ops.reverse_neighbors(idx, c.Ns) if use_rev else None
+    y, min_d2 = ops.kpconv(q, s, idx, x, kp, W, dc.EXTENT, c.influence, "sum", offsets=off, modulations=mod, rev=rev)
+    ((y * T(i.g)).sum() + (min_d2 * T(i.gm)).sum()).backward()
+    dead, zero = dc.shadow_rows(name), _zero_rows(name)
+    lab = "deform %s %s: " % (name, "gather" if use_rev else "scatter")
+    dc.compare(lab + "y", N(y), o.y, FP_TOL)
+    dc.compare(lab + "min_d2", N(min_d2), o.min_d2, FP_TOL, dead)
+    dc.compare(lab + "dW", N(W.grad), o.dW, FP_TOL)
+    dc.compare(lab + "dx", N(x.grad), o.dx, DEFORM_TOL)
+    dc.compare(lab + "d_offsets", N(off.grad), o.d_offsets, DEFORM_TOL, dead)
+    if c.mod:
+        dc.compare(lab + "d_modulations", N(mod.grad), o.d_modulations, DEFORM_TOL)
+    assert not N(y)[zero].any()
+    dc.compare(lab + "d_offsets of the rows that keep nothing = min_d2 term", N(off.grad)[zero],
+               o.diag["d_offsets_min"][zero], DEFORM_TOL, dead[zero])
+
+
+@pytest.mark.parametrize("name", [c.name for c in dc.CASES])
+def test_deformable_aggregate_and_a_path_offset_gradient(ops, name):
+    """The two halves taken apart. Forward: the aggregate A and min_d2 of ops.kpconv_gather(..., want_min_d2=True), exactly
+    zero in the rows that keep nothing. Backward: the A path of d_offsets alone (no g_min_d2) from the scatter entry point
+    under the case's influence and, for the linear cases, from ops.kpconv_deform_doff directly -- exactly zero in the
+    rows that keep nothing (constant influence: everywhere)."""
+    c, i, o = dc.BY_NAME[name], dc.make_inputs(name), dc.oracle64(name)
+    q, s, idx, kp, x, off = T(i.q), T(i.s), T(i.idx), T(i.kp), T(i.x), T(i.offsets)
+    dead, zero = dc.shadow_rows(name), _zero_rows(name)
+    lab = "deform %s direct: " % name
+    A, min_d2 = ops.kpconv_gather(q, s, idx, x, kp, dc.EXTENT, c.influence, "sum", offsets=off, want_min_d2=True)
+    dc.compare(lab + "A", N(A), o.A, FP_TOL)
+    dc.compare(lab + "min_d2", N(min_d2), o.min_d2, FP_TOL, dead)
+    assert not N(A)[zero].any()
+    want = o.d_offsets - o.diag["d_offsets_min"]
+    dA = T(o.diag["dA"].astype(np.float32))
+    dx, d_off = ops.kpconv_scatter(q, s, idx, dA, kp, dc.EXTENT, c.influence, "sum", x=x, offsets=off)
+    dc.compare(lab + "dx (scatter entry point)", N(dx), o.dx, DEFORM_TOL)
+    dc.compare(lab + "d_offsets A path (scatter entry point)", N(d_off), want, DEFORM_TOL)
+    assert not N(d_off)[zero].any()
+    if c.influence == "constant":
+        assert not want.any() and not N(d_off).any()
+    if c.influence == "linear":
+        d_off = ops.kpconv_deform_doff(q, s, idx, x, kp, dc.EXTENT, off, dA)
+        dc.compare(lab + "d_offsets A path (kpconv_deform_doff)", N(d_off), want, DEFORM_TOL)
+        assert not N(d_off)[zero].any()
+
+
+def test_deformable_closest_backward_is_a_loud_error(ops):
+    """Deformable + `closest` aggregation has a forward (kpconv_gather_vec<DEFORM>) and no offset-gradient path: the
+    backward raises on the host."""
+    i = dc.make_inputs("m20")
+    x, off = T(i.x).requires_grad_(True), T(i.offsets).requires_grad_(True)
+    y, min_d2 = ops.kpconv(T(i.q), T(i.s), T(i.idx), x, T(i.kp), T(i.W), dc.EXTENT, "linear", "closest", offsets=off)
+    with pytest.raises(RuntimeError, match="closest"):
+        (y * T(i.g)).sum().backward()
+    assert x.grad is None and off.grad is None
+
+
+def test_offset_gradient_rows_too_wide_for_the_lds_staging_are_a_loud_error(ops):
+    """kpconv_deform_doff stages 16 x Cin4 floats of dA in LDS: the smallest Cin with Cin % 4 != 0 past the 160 KiB the
+    host code allows is refused before anything is launched (the widest that fits is case v2551 of the sweep)."""
+    c = dc.BY_NAME["v2551"]
+    cin = next(n for n in range(1, 1 << 14) if n % 4 and dc.doff_vector_lds(n, c.H, c.Nq) > 160 * 1024)
+    assert cin == 2553 and dc.doff_vector_lds(c.cin, c.H, c.Nq) <= 160 * 1024
+    i = dc.make_inputs("v2551")
+    x = torch.zeros(c.Ns, cin, device="cuda")
+    dA = torch.zeros(c.Nq, c.K, cin, device="cuda")
+    with pytest.raises(RuntimeError, match="does not fit the LDS staging"):
+        ops.kpconv_deform_doff(T(i.q), T(i.s), T(i.idx), x, T(i.kp), dc.EXTENT, T(i.offsets), dA)
