@@ -12,7 +12,6 @@
 //   stats  : mean[D], invstd[D]  (+ running_mean / running_var update, unbiased variance)
 //   apply  : y = leaky( (x - mean) * invstd * gamma + beta ), rows >= n_valid -> 0
 //   bwd    : dgamma, dbeta, dx   (g masked through the LeakyReLU by recomputing the sign)
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -164,54 +163,6 @@ __device__ __forceinline__ bool bn_sum_partials_m2(const float* __restrict__ par
   return true;
 }
 
-// grid ceil(D/64), block 1024
-__global__ __launch_bounds__(1024) void bn_stats_finish(const float* __restrict__ x, const int* __restrict__ n_valid,
-                                                        int R, int D, const float* __restrict__ part, float eps,
-                                                        float momentum, float* __restrict__ mean,
-                                                        float* __restrict__ invstd, float* __restrict__ running_mean,
-                                                        float* __restrict__ running_var, long long* __restrict__ nbt) {
-  if (nbt && blockIdx.x == 0 && threadIdx.x == 0) *nbt += 1;   // num_batches_tracked (nn.BatchNorm bookkeeping)
-  float p1, p2;
-  if (!bn_sum_partials(part, (R + BN_ROWS - 1) / BN_ROWS, D, &p1, &p2)) return;
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int n = min(*n_valid, R);
-  if (n < 1) {
-    mean[c] = 0.f;
-    invstd[c] = 0.f;
-    return;
-  }
-  const float k = x[c];
-  const float m1 = p1 / (float)n, m2 = p2 / (float)n;
-  const float mu = k + m1;
-  float var = m2 - m1 * m1;  // biased
-  var = var > 0.f ? var : 0.f;
-  mean[c] = mu;
-  invstd[c] = rsqrtf(var + eps);
-  if (running_mean) {
-    const float unbiased = n > 1 ? var * ((float)n / (float)(n - 1)) : var;
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
-  }
-}
-
-__global__ void bn_apply(const float* __restrict__ x, const int* __restrict__ n_valid, int R, int D,
-                         const float* __restrict__ mean, const float* __restrict__ invstd,
-                         const float* __restrict__ gamma, const float* __restrict__ beta, float slope,
-                         const float* __restrict__ addend, float* __restrict__ y) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (int64_t)R * D) return;
-  const int n = min(*n_valid, R);
-  const int c = (int)(t % D);
-  const int64_t r = t / D;
-  float v = 0.f;
-  if (r < n) {
-    v = (x[t] - mean[c]) * invstd[c] * gamma[c] + beta[c];
-    if (addend) v += addend[t];   // residual join (blocks.py:649) fused with its LeakyReLU
-    v = v > 0.f ? v : v * slope;
-  }
-  y[t] = v;
-}
-
 // dbeta[c] = sum g', dgamma[c] = sum g' * xhat   (g' = g through the LeakyReLU)
 __device__ __forceinline__ void bn_bwd_reduce_body(const float* __restrict__ x, const float* __restrict__ g,
                                                       const int* __restrict__ n_valid, int R, int D,
@@ -265,66 +216,23 @@ __device__ __forceinline__ void bn_bwd_reduce_body(const float* __restrict__ x, 
   }
 }
 
-__global__ __launch_bounds__(BN_T) void bn_bwd_reduce(const float* __restrict__ x, const float* __restrict__ g,
-                                                      const int* __restrict__ n_valid, int R, int D,
-                                                      const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                      float slope, const float* __restrict__ yout,
-                                                      float* __restrict__ part /* [nblk,2,D] */) {
-  bn_bwd_reduce_body(x, g, n_valid, R, D, mean, invstd, gamma, beta, slope, yout, part);
-}
-
-// two independent problems of the same row count in one launch (blockIdx.z): the BatchNorm of a bottleneck block's
-// convolution and the one of its shortcut (blocks.py:596-649) -- a launch of this chain costs more than its work
-struct bn_bwd_reduce_args {
-  const float* x;
-  const float* g;
-  const int* n_valid;
-  int R;
-  int D;
-  const float* mean;
-  const float* invstd;
-  const float* gamma;
-  const float* beta;
-  float slope;
-  const float* yout;
-  float* part;
+// The problems of one launch, passed by value (include/mvkpconv.h: mvk_bn_fwd_problem / _bwd_problem). NP = 2: two
+// independent problems of the same row count, picked by blockIdx.z -- the BatchNorm of a bottleneck block's convolution
+// and the one of its shortcut (blocks.py:596-649); a launch of this chain costs more than its work.
+template <class P, int NP>
+struct bn_problems {
+  P p[NP];
+  __device__ __forceinline__ const P& mine() const { return p[NP == 2 ? blockIdx.z : 0]; }
 };
-__global__ __launch_bounds__(BN_T) void bn_bwd_reduce_pair(bn_bwd_reduce_args a0, bn_bwd_reduce_args a1) {
-  const bn_bwd_reduce_args& a = blockIdx.z ? a1 : a0;
-  bn_bwd_reduce_body(a.x, a.g, a.n_valid, a.R, a.D, a.mean, a.invstd, a.gamma, a.beta, a.slope, a.yout, a.part);
-}
+template <int NP>
+using bn_fwd_problems = bn_problems<mvk_bn_fwd_problem, NP>;   // ext_part: the partials to reduce (the host puts scratch2D there)
+template <int NP>
+using bn_bwd_problems = bn_problems<mvk_bn_bwd_problem, NP>;
 
-__global__ __launch_bounds__(1024) void bn_bwd_finish(const float* __restrict__ part, int R, int D,
-                                                      float* __restrict__ dgb /* [2,D] */) {
-  float a, b;
-  if (!bn_sum_partials(part, (R + BN_ROWS - 1) / BN_ROWS, D, &a, &b)) return;
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  dgb[c] = a;
-  dgb[D + c] = b;
-}
-
-__global__ void bn_bwd_apply(const float* __restrict__ x, const float* __restrict__ g,
-                             const int* __restrict__ n_valid, int R, int D, const float* __restrict__ mean,
-                             const float* __restrict__ invstd, const float* __restrict__ gamma,
-                             const float* __restrict__ beta, float slope, const float* __restrict__ part,
-                             const float* __restrict__ yout, float* __restrict__ d_addend, float* __restrict__ dx) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (int64_t)R * D) return;
-  const int n = min(*n_valid, R);
-  const int c = (int)(t % D);
-  const int64_t r = t / D;
-  float v = 0.f, ga_out = 0.f;
-  if (r < n) {
-    const float xh = (x[t] - mean[c]) * invstd[c];
-    float gv = g[t];
-    if (yout ? yout[t] <= 0.f : xh * gamma[c] + beta[c] <= 0.f) gv *= slope;
-    const float inv_n = 1.f / (float)n;
-    v = gamma[c] * invstd[c] * (gv - part[c] * inv_n - xh * part[D + c] * inv_n);
-    ga_out = gv;
-  }
-  dx[t] = v;
-  if (d_addend) d_addend[t] = ga_out;
+template <int NP>
+__global__ __launch_bounds__(BN_T) void bn_bwd_reduce(bn_bwd_problems<NP> a) {
+  const mvk_bn_bwd_problem& p = a.mine();
+  bn_bwd_reduce_body(p.x, p.g, p.n_valid, (int)p.R, p.D, p.mean, p.invstd, p.gamma, p.beta, p.slope, p.y_out, p.scratch);
 }
 
 // ---- finish + apply in one launch: every workgroup of the apply grid first reduces the per-row-block
@@ -332,17 +240,8 @@ __global__ void bn_bwd_apply(const float* __restrict__ x, const float* __restric
 // mean / invstd bit for bit; nblk x 512 bytes from L2, at most 64 workgroups per channel group do it), then
 // normalises its share of the rows. 3 graph nodes -> 2 per BatchNorm pass; the first row-group publishes
 // mean / invstd (saved for the backward), the running statistics and the batch counter.
-//   grid (ceil(D/64), gy <= 64), block 1024 = 64 channels x 16 row lanes; rows are dealt round-robin.
-constexpr int BN_FUSED_GY_DEFAULT = 128;   // measured: 5.62 ms per step at 64 row groups, 5.53 at 128, 5.51 at 256
-int bn_fused_gy() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("MVK_BN_FUSED_GY");
-    v = e ? atoi(e) : BN_FUSED_GY_DEFAULT;
-    if (v < 1) v = 1;
-  }
-  return v;
-}
+//   grid (ceil(D/64), gy <= BN_FUSED_GY), block 1024 = 64 channels x 16 row lanes; rows are dealt round-robin.
+constexpr int BN_FUSED_GY = 128;   // measured: 5.62 ms per step at 64 row groups, 5.53 at 128, 5.51 at 256
 
 __device__ __forceinline__ void bn_finish_apply_body(const float* __restrict__ x, const int* __restrict__ n_valid, int R,
                                                         int D, const float* __restrict__ part, float eps, float momentum,
@@ -431,41 +330,11 @@ __device__ __forceinline__ void bn_finish_apply_body(const float* __restrict__ x
   }
 }
 
-__global__ __launch_bounds__(1024) void bn_finish_apply(const float* __restrict__ x, const int* __restrict__ n_valid, int R,
-                                                        int D, const float* __restrict__ part, float eps, float momentum,
-                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                        float slope, float* __restrict__ mean, float* __restrict__ invstd,
-                                                        float* __restrict__ running_mean, float* __restrict__ running_var,
-                                                        long long* __restrict__ nbt, const float* __restrict__ addend,
-                                                        float* __restrict__ y, int ext_rows) {
-  bn_finish_apply_body(x, n_valid, R, D, part, eps, momentum, gamma, beta, slope, mean, invstd, running_mean, running_var, nbt, addend, y, ext_rows);
-}
-
-// two independent problems of the same row count in one launch (blockIdx.z): the BatchNorm of a bottleneck block's
-// convolution and the one of its shortcut (blocks.py:596-649) -- a launch of this chain costs more than its work
-struct bn_finish_apply_args {
-  const float* x;
-  const int* n_valid;
-  int R;
-  int D;
-  const float* part;
-  float eps;
-  float momentum;
-  const float* gamma;
-  const float* beta;
-  float slope;
-  float* mean;
-  float* invstd;
-  float* running_mean;
-  float* running_var;
-  long long* nbt;
-  const float* addend;
-  float* y;
-  int ext_rows;
-};
-__global__ __launch_bounds__(1024) void bn_finish_apply_pair(bn_finish_apply_args a0, bn_finish_apply_args a1) {
-  const bn_finish_apply_args& a = blockIdx.z ? a1 : a0;
-  bn_finish_apply_body(a.x, a.n_valid, a.R, a.D, a.part, a.eps, a.momentum, a.gamma, a.beta, a.slope, a.mean, a.invstd, a.running_mean, a.running_var, a.nbt, a.addend, a.y, a.ext_rows);
+template <int NP>
+__global__ __launch_bounds__(1024) void bn_finish_apply(bn_fwd_problems<NP> a) {
+  const mvk_bn_fwd_problem& p = a.mine();
+  bn_finish_apply_body(p.x, p.n_valid, (int)p.R, p.D, p.ext_part, p.eps, p.momentum, p.gamma, p.beta, p.slope, p.mean, p.invstd,
+                       p.running_mean, p.running_var, (long long*)p.num_batches_tracked, p.addend, p.y, p.ext_rows);
 }
 
 __device__ __forceinline__ void bn_bwd_finish_apply_body(const float* __restrict__ x, const float* __restrict__ g,
@@ -532,52 +401,16 @@ __device__ __forceinline__ void bn_bwd_finish_apply_body(const float* __restrict
   }
 }
 
-__global__ __launch_bounds__(1024) void bn_bwd_finish_apply(const float* __restrict__ x, const float* __restrict__ g,
-                                                            const int* __restrict__ n_valid, int R, int D,
-                                                            const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                            float slope, const float* __restrict__ part,
-                                                            const float* __restrict__ yout, float* __restrict__ d_addend,
-                                                            float* __restrict__ dgb, float* __restrict__ dx) {
-  bn_bwd_finish_apply_body(x, g, n_valid, R, D, mean, invstd, gamma, beta, slope, part, yout, d_addend, dgb, dx);
-}
-
-// two independent problems of the same row count in one launch (blockIdx.z): the BatchNorm of a bottleneck block's
-// convolution and the one of its shortcut (blocks.py:596-649) -- a launch of this chain costs more than its work
-struct bn_bwd_finish_apply_args {
-  const float* x;
-  const float* g;
-  const int* n_valid;
-  int R;
-  int D;
-  const float* mean;
-  const float* invstd;
-  const float* gamma;
-  const float* beta;
-  float slope;
-  const float* part;
-  const float* yout;
-  float* d_addend;
-  float* dgb;
-  float* dx;
-};
-__global__ __launch_bounds__(1024) void bn_bwd_finish_apply_pair(bn_bwd_finish_apply_args a0, bn_bwd_finish_apply_args a1) {
-  const bn_bwd_finish_apply_args& a = blockIdx.z ? a1 : a0;
-  bn_bwd_finish_apply_body(a.x, a.g, a.n_valid, a.R, a.D, a.mean, a.invstd, a.gamma, a.beta, a.slope, a.part, a.yout, a.d_addend, a.dgb, a.dx);
-}
-
-bool bn_fused_finish() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("MVK_BN_FUSED_FINISH");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
+template <int NP>
+__global__ __launch_bounds__(1024) void bn_bwd_finish_apply(bn_bwd_problems<NP> a) {
+  const mvk_bn_bwd_problem& p = a.mine();
+  bn_bwd_finish_apply_body(p.x, p.g, p.n_valid, (int)p.R, p.D, p.mean, p.invstd, p.gamma, p.beta, p.slope, p.scratch, p.y_out,
+                           p.d_addend, p.dgamma_dbeta, p.dx);
 }
 
 // ---- small tensors (coarse pyramid levels): one workgroup per 64 channels does statistics AND
 // normalisation in a single launch (the rows are re-read from L2), 3 kernel nodes -> 1.
-constexpr int BN_SMALL_ROWS_DEFAULT = 128;   // measured: above ~128 rows three parallel launches beat one workgroup per 64 channels
+constexpr int BN_SMALL_ROWS = 128;   // measured: above ~128 rows parallel launches beat one workgroup per 64 channels
 
 __device__ __forceinline__ void block_sum2(float& a, float& b, float (*r1)[64], float (*r2)[64]) {
   const int cl = threadIdx.x & 63, pr = threadIdx.x >> 6;
@@ -652,39 +485,11 @@ __device__ __forceinline__ void bn_small_fwd_body(const float* __restrict__ x, c
   }
 }
 
-__global__ __launch_bounds__(1024) void bn_small_fwd(const float* __restrict__ x, const int* __restrict__ n_valid, int R,
-                                                     int D, const float* __restrict__ gamma,
-                                                     const float* __restrict__ beta, float eps, float momentum,
-                                                     float slope, float* __restrict__ running_mean,
-                                                     float* __restrict__ running_var, float* __restrict__ mean,
-                                                     float* __restrict__ invstd, float* __restrict__ y,
-                                                     long long* __restrict__ nbt, const float* __restrict__ addend) {
-  bn_small_fwd_body(x, n_valid, R, D, gamma, beta, eps, momentum, slope, running_mean, running_var, mean, invstd, y, nbt, addend);
-}
-
-// two independent problems of the same row count in one launch (blockIdx.z): the BatchNorm of a bottleneck block's
-// convolution and the one of its shortcut (blocks.py:596-649) -- a launch of this chain costs more than its work
-struct bn_small_fwd_args {
-  const float* x;
-  const int* n_valid;
-  int R;
-  int D;
-  const float* gamma;
-  const float* beta;
-  float eps;
-  float momentum;
-  float slope;
-  float* running_mean;
-  float* running_var;
-  float* mean;
-  float* invstd;
-  float* y;
-  long long* nbt;
-  const float* addend;
-};
-__global__ __launch_bounds__(1024) void bn_small_fwd_pair(bn_small_fwd_args a0, bn_small_fwd_args a1) {
-  const bn_small_fwd_args& a = blockIdx.z ? a1 : a0;
-  bn_small_fwd_body(a.x, a.n_valid, a.R, a.D, a.gamma, a.beta, a.eps, a.momentum, a.slope, a.running_mean, a.running_var, a.mean, a.invstd, a.y, a.nbt, a.addend);
+template <int NP>
+__global__ __launch_bounds__(1024) void bn_small_fwd(bn_fwd_problems<NP> a) {
+  const mvk_bn_fwd_problem& p = a.mine();
+  bn_small_fwd_body(p.x, p.n_valid, (int)p.R, p.D, p.gamma, p.beta, p.eps, p.momentum, p.slope, p.running_mean, p.running_var,
+                    p.mean, p.invstd, p.y, (long long*)p.num_batches_tracked, p.addend);
 }
 
 __device__ __forceinline__ void bn_small_bwd_body(const float* __restrict__ x, const float* __restrict__ g,
@@ -731,45 +536,18 @@ __device__ __forceinline__ void bn_small_bwd_body(const float* __restrict__ x, c
   }
 }
 
-__global__ __launch_bounds__(1024) void bn_small_bwd(const float* __restrict__ x, const float* __restrict__ g,
-                                                     const int* __restrict__ n_valid, int R, int D,
-                                                     const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                     float slope, const float* __restrict__ yout,
-                                                     float* __restrict__ d_addend, float* __restrict__ dgb,
-                                                     float* __restrict__ dx) {
-  bn_small_bwd_body(x, g, n_valid, R, D, mean, invstd, gamma, beta, slope, yout, d_addend, dgb, dx);
-}
-
-// two independent problems of the same row count in one launch (blockIdx.z): the BatchNorm of a bottleneck block's
-// convolution and the one of its shortcut (blocks.py:596-649) -- a launch of this chain costs more than its work
-struct bn_small_bwd_args {
-  const float* x;
-  const float* g;
-  const int* n_valid;
-  int R;
-  int D;
-  const float* mean;
-  const float* invstd;
-  const float* gamma;
-  const float* beta;
-  float slope;
-  const float* yout;
-  float* d_addend;
-  float* dgb;
-  float* dx;
-};
-__global__ __launch_bounds__(1024) void bn_small_bwd_pair(bn_small_bwd_args a0, bn_small_bwd_args a1) {
-  const bn_small_bwd_args& a = blockIdx.z ? a1 : a0;
-  bn_small_bwd_body(a.x, a.g, a.n_valid, a.R, a.D, a.mean, a.invstd, a.gamma, a.beta, a.slope, a.yout, a.d_addend, a.dgb, a.dx);
+template <int NP>
+__global__ __launch_bounds__(1024) void bn_small_bwd(bn_bwd_problems<NP> a) {
+  const mvk_bn_bwd_problem& p = a.mine();
+  bn_small_bwd_body(p.x, p.g, p.n_valid, (int)p.R, p.D, p.mean, p.invstd, p.gamma, p.beta, p.slope, p.y_out, p.d_addend,
+                    p.dgamma_dbeta, p.dx);
 }
 
 // ---- the same single-launch BatchNorm for 129..1024 rows and D % 4 == 0, latency-shaped: a workgroup owns 16
 // channels (4 quads x 256 row lanes), a thread holds ALL its rows (at most 4) of x (and g, y) as float4 in
 // registers -- one round of loads, a reduction over the 256 row lanes (wave shuffles, then 16 partials through LDS),
 // one round of stores. The two-launch path costs a second kernel node (~8 us in a graph) and a re-read of x.
-constexpr int BN_MID_ROWS_DEFAULT = 1024;
-constexpr int BN_MID_MAX = 1024;      // 4 rows per thread x 256 row lanes
+constexpr int BN_MID_ROWS = 1024;     // = 4 rows per thread x 256 row lanes, all a thread can hold
 
 // dflt unless cond, then the 16 bytes at p (written as a branch: `cond ? *p : dflt` on a struct becomes a select of
 // POINTERS -- the default spilled to scratch and a flat load)
@@ -804,7 +582,7 @@ __device__ __forceinline__ void mid_sum(float4& a, float4& b, float4 (*ra)[4], f
   b = y;
 }
 
-// grid ceil(D/16), block 1024 = 4 channel quads x 256 row lanes; R <= BN_MID_MAX
+// grid ceil(D/16), block 1024 = 4 channel quads x 256 row lanes; R <= BN_MID_ROWS
 __device__ __forceinline__ void bn_mid_fwd_body(const float* __restrict__ x, const int* __restrict__ n_valid, int R,
                                                    int D, const float* __restrict__ gamma,
                                                    const float* __restrict__ beta, float eps, float momentum,
@@ -887,39 +665,11 @@ __device__ __forceinline__ void bn_mid_fwd_body(const float* __restrict__ x, con
   }
 }
 
-__global__ __launch_bounds__(1024) void bn_mid_fwd(const float* __restrict__ x, const int* __restrict__ n_valid, int R,
-                                                   int D, const float* __restrict__ gamma,
-                                                   const float* __restrict__ beta, float eps, float momentum,
-                                                   float slope, float* __restrict__ running_mean,
-                                                   float* __restrict__ running_var, float* __restrict__ mean,
-                                                   float* __restrict__ invstd, float* __restrict__ y,
-                                                   long long* __restrict__ nbt, const float* __restrict__ addend) {
-  bn_mid_fwd_body(x, n_valid, R, D, gamma, beta, eps, momentum, slope, running_mean, running_var, mean, invstd, y, nbt, addend);
-}
-
-// two independent problems of the same row count in one launch (blockIdx.z): the BatchNorm of a bottleneck block's
-// convolution and the one of its shortcut (blocks.py:596-649) -- a launch of this chain costs more than its work
-struct bn_mid_fwd_args {
-  const float* x;
-  const int* n_valid;
-  int R;
-  int D;
-  const float* gamma;
-  const float* beta;
-  float eps;
-  float momentum;
-  float slope;
-  float* running_mean;
-  float* running_var;
-  float* mean;
-  float* invstd;
-  float* y;
-  long long* nbt;
-  const float* addend;
-};
-__global__ __launch_bounds__(1024) void bn_mid_fwd_pair(bn_mid_fwd_args a0, bn_mid_fwd_args a1) {
-  const bn_mid_fwd_args& a = blockIdx.z ? a1 : a0;
-  bn_mid_fwd_body(a.x, a.n_valid, a.R, a.D, a.gamma, a.beta, a.eps, a.momentum, a.slope, a.running_mean, a.running_var, a.mean, a.invstd, a.y, a.nbt, a.addend);
+template <int NP>
+__global__ __launch_bounds__(1024) void bn_mid_fwd(bn_fwd_problems<NP> a) {
+  const mvk_bn_fwd_problem& p = a.mine();
+  bn_mid_fwd_body(p.x, p.n_valid, (int)p.R, p.D, p.gamma, p.beta, p.eps, p.momentum, p.slope, p.running_mean, p.running_var,
+                  p.mean, p.invstd, p.y, (long long*)p.num_batches_tracked, p.addend);
 }
 
 __device__ __forceinline__ void bn_mid_bwd_body(const float* __restrict__ x, const float* __restrict__ g,
@@ -983,37 +733,11 @@ __device__ __forceinline__ void bn_mid_bwd_body(const float* __restrict__ x, con
   }
 }
 
-__global__ __launch_bounds__(1024) void bn_mid_bwd(const float* __restrict__ x, const float* __restrict__ g,
-                                                   const int* __restrict__ n_valid, int R, int D,
-                                                   const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                   float slope, const float* __restrict__ yout,
-                                                   float* __restrict__ d_addend, float* __restrict__ dgb,
-                                                   float* __restrict__ dx) {
-  bn_mid_bwd_body(x, g, n_valid, R, D, mean, invstd, gamma, beta, slope, yout, d_addend, dgb, dx);
-}
-
-// two independent problems of the same row count in one launch (blockIdx.z): the BatchNorm of a bottleneck block's
-// convolution and the one of its shortcut (blocks.py:596-649) -- a launch of this chain costs more than its work
-struct bn_mid_bwd_args {
-  const float* x;
-  const float* g;
-  const int* n_valid;
-  int R;
-  int D;
-  const float* mean;
-  const float* invstd;
-  const float* gamma;
-  const float* beta;
-  float slope;
-  const float* yout;
-  float* d_addend;
-  float* dgb;
-  float* dx;
-};
-__global__ __launch_bounds__(1024) void bn_mid_bwd_pair(bn_mid_bwd_args a0, bn_mid_bwd_args a1) {
-  const bn_mid_bwd_args& a = blockIdx.z ? a1 : a0;
-  bn_mid_bwd_body(a.x, a.g, a.n_valid, a.R, a.D, a.mean, a.invstd, a.gamma, a.beta, a.slope, a.yout, a.d_addend, a.dgb, a.dx);
+template <int NP>
+__global__ __launch_bounds__(1024) void bn_mid_bwd(bn_bwd_problems<NP> a) {
+  const mvk_bn_bwd_problem& p = a.mine();
+  bn_mid_bwd_body(p.x, p.g, p.n_valid, (int)p.R, p.D, p.mean, p.invstd, p.gamma, p.beta, p.slope, p.y_out, p.d_addend,
+                  p.dgamma_dbeta, p.dx);
 }
 
 // ---- y = LeakyReLU(a + b) (the residual join of ResnetBottleneckBlock, blocks.py:649) in one launch
@@ -1032,16 +756,6 @@ __global__ void add_lrelu_bwd_k(const float* __restrict__ y, const float* __rest
   d[t] = y[t] > 0.f ? g[t] : g[t] * slope;   // slope > 0: sign(y) == sign(a + b)
 }
 
-// rows up to which the single-launch kernels are used (development override: MVK_BN_SMALL_ROWS)
-int bn_small_rows() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("MVK_BN_SMALL_ROWS");
-    v = e ? atoi(e) : BN_SMALL_ROWS_DEFAULT;
-  }
-  return v;
-}
-
 // every non-null pointer 16-byte aligned (the vectorised kernels load float4)
 bool aligned16(const void* a, const void* b, const void* c, const void* d, const void* e, const void* f, const void* g,
                const void* h) {
@@ -1049,135 +763,12 @@ bool aligned16(const void* a, const void* b, const void* c, const void* d, const
            (uintptr_t)h) & 15) == 0;
 }
 
-// rows up to which the vectorised single-launch kernels are used when D % 4 == 0 (MVK_BN_MID_ROWS)
-int bn_mid_rows() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("MVK_BN_MID_ROWS");
-    v = e ? atoi(e) : BN_MID_ROWS_DEFAULT;
-    if (v > BN_MID_MAX) v = BN_MID_MAX;
-  }
-  return v;
-}
-
-}  // namespace
-
-// rows up to which mvk_bn_lrelu_fwd / _bwd are ONE launch for a D-channel input (a producer need not emit statistics)
-extern "C" int mvk_bn_single_launch_rows(int D) {
-  static const bool keep_stats = getenv("MVK_BN_MID_KEEP_STATS") != nullptr;     // development: producers still emit partials
-  if (keep_stats) return bn_small_rows();
-  return (D % 4 == 0 && bn_mid_rows() > bn_small_rows()) ? bn_mid_rows() : bn_small_rows();
-}
-
-extern "C" int mvk_bn_lrelu_fwd(const float* x, const int32_t* n_valid, int64_t R, int D, const float* gamma,
-                                const float* beta, float eps, float momentum, float slope, float* running_mean,
-                                float* running_var, float* mean, float* invstd, float* scratch2D /* [ceil(R/64),2,D] */, float* y,
-                                int64_t* num_batches_tracked, const float* addend, const float* ext_part, int ext_rows,
-                                void* stream) {
-  MVK_REQUIRE(R >= 0 && D > 0 && R < (1ll << 31), "bn: bad sizes");
-  MVK_REQUIRE((ext_part == nullptr) == (ext_rows <= 0) && ext_rows >= -1, "bn: ext_part and ext_rows go together (-1: finished statistics)");
-  if (R == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (ext_rows < 0) {      // mean / invstd finished by the producing GEMM: the apply pass alone, whatever the row count
-    MVK_REQUIRE(bn_fused_finish(), "bn: finished statistics need the fused apply kernel (MVK_BN_FUSED_FINISH=1)");
-    const unsigned gyr = (unsigned)cdiv64(R, BN_ROWS);
-    const unsigned gy = gyr < (unsigned)bn_fused_gy() ? gyr : (unsigned)bn_fused_gy();
-    hipLaunchKernelGGL(bn_finish_apply, dim3((unsigned)cdiv64(D, 64), gy), dim3(1024), 0, st, x, n_valid, (int)R, D, nullptr,
-                       eps, momentum, gamma, beta, slope, mean, invstd, nullptr, nullptr, nullptr, addend, y, -1);
-    MVK_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-  if (R > bn_small_rows() && R <= bn_mid_rows() && D % 4 == 0 &&
-      aligned16(x, y, addend, gamma, beta, mean, invstd, running_mean) &&
-      aligned16(running_var, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) {
-    hipLaunchKernelGGL(bn_mid_fwd, dim3((unsigned)cdiv64(D, 16)), dim3(1024), 0, st, x, n_valid, (int)R, D, gamma, beta,
-                       eps, momentum, slope, running_mean, running_var, mean, invstd, y, (long long*)num_batches_tracked, addend);
-    MVK_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-  if (R <= bn_small_rows()) {
-    hipLaunchKernelGGL(bn_small_fwd, dim3((unsigned)cdiv64(D, 64)), dim3(1024), 0, st, x, n_valid, (int)R, D, gamma, beta,
-                       eps, momentum, slope, running_mean, running_var, mean, invstd, y, (long long*)num_batches_tracked, addend);
-    MVK_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-  dim3 g1((unsigned)cdiv64(D, 64), (unsigned)cdiv64(R, BN_ROWS));
-  if (ext_part && bn_fused_finish()) {       // statistics already produced by the GEMM epilogue: one launch
-    const unsigned gy = g1.y < (unsigned)bn_fused_gy() ? g1.y : (unsigned)bn_fused_gy();
-    hipLaunchKernelGGL(bn_finish_apply, dim3(g1.x, gy), dim3(1024), 0, st, x, n_valid, (int)R, D, ext_part, eps, momentum,
-                       gamma, beta, slope, mean, invstd, running_mean, running_var, (long long*)num_batches_tracked, addend, y,
-                       ext_rows);
-    MVK_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-  hipLaunchKernelGGL(bn_stats_partial, g1, dim3(BN_T), 0, st, x, n_valid, (int)R, D, scratch2D);
-  if (bn_fused_finish()) {
-    const unsigned gy = g1.y < (unsigned)bn_fused_gy() ? g1.y : (unsigned)bn_fused_gy();
-    hipLaunchKernelGGL(bn_finish_apply, dim3(g1.x, gy), dim3(1024), 0, st, x, n_valid, (int)R, D, scratch2D, eps, momentum,
-                       gamma, beta, slope, mean, invstd, running_mean, running_var, (long long*)num_batches_tracked, addend, y, 0);
-    MVK_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-  hipLaunchKernelGGL(bn_stats_finish, dim3((unsigned)cdiv64(D, 64)), dim3(1024), 0, st, x, n_valid, (int)R, D, scratch2D,
-                     eps, momentum, mean, invstd, running_mean, running_var, (long long*)num_batches_tracked);
-  hipLaunchKernelGGL(bn_apply, dim3((unsigned)cdiv64(R * D, 256)), dim3(256), 0, st, x, n_valid, (int)R, D, mean, invstd,
-                     gamma, beta, slope, addend, y);
-  MVK_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-extern "C" int mvk_bn_lrelu_bwd(const float* x, const float* g, const int32_t* n_valid, int64_t R, int D,
-                                const float* gamma, const float* beta, const float* mean, const float* invstd,
-                                float slope, float* scratch /* [ceil(R/64),2,D] */,
-                                float* dgamma_dbeta /* [2,D]: dbeta then dgamma */, float* dx, const float* y_out,
-                                float* d_addend, void* stream) {
-  MVK_REQUIRE(R >= 0 && D > 0 && R < (1ll << 31), "bn: bad sizes");
-  MVK_REQUIRE((y_out == nullptr) == (d_addend == nullptr), "bn: y_out and d_addend go together (residual-join mode)");
-  hipStream_t st = (hipStream_t)stream;
-  if (R == 0) {
-    MVK_CHECK_HIP(hipMemsetAsync(dgamma_dbeta, 0, sizeof(float) * 2 * D, st));
-    return 0;
-  }
-  if (R > bn_small_rows() && R <= bn_mid_rows() && D % 4 == 0 &&
-      aligned16(x, g, y_out, d_addend, dgamma_dbeta, dx, mean, invstd) && aligned16(gamma, beta, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) {
-    hipLaunchKernelGGL(bn_mid_bwd, dim3((unsigned)cdiv64(D, 16)), dim3(1024), 0, st, x, g, n_valid, (int)R, D, mean,
-                       invstd, gamma, beta, slope, y_out, d_addend, dgamma_dbeta, dx);
-    MVK_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-  if (R <= bn_small_rows()) {
-    hipLaunchKernelGGL(bn_small_bwd, dim3((unsigned)cdiv64(D, 64)), dim3(1024), 0, st, x, g, n_valid, (int)R, D, mean,
-                       invstd, gamma, beta, slope, y_out, d_addend, dgamma_dbeta, dx);
-    MVK_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-  dim3 g1((unsigned)cdiv64(D, 64), (unsigned)cdiv64(R, BN_ROWS));
-  hipLaunchKernelGGL(bn_bwd_reduce, g1, dim3(BN_T), 0, st, x, g, n_valid, (int)R, D, mean, invstd, gamma, beta, slope,
-                     y_out, scratch);
-  if (bn_fused_finish()) {
-    const unsigned gy = g1.y < (unsigned)bn_fused_gy() ? g1.y : (unsigned)bn_fused_gy();
-    hipLaunchKernelGGL(bn_bwd_finish_apply, dim3(g1.x, gy), dim3(1024), 0, st, x, g, n_valid, (int)R, D, mean, invstd, gamma,
-                       beta, slope, scratch, y_out, d_addend, dgamma_dbeta, dx);
-    MVK_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-  hipLaunchKernelGGL(bn_bwd_finish, dim3((unsigned)cdiv64(D, 64)), dim3(1024), 0, st, scratch, (int)R, D, dgamma_dbeta);
-  hipLaunchKernelGGL(bn_bwd_apply, dim3((unsigned)cdiv64(R * D, 256)), dim3(256), 0, st, x, g, n_valid, (int)R, D, mean,
-                     invstd, gamma, beta, slope, dgamma_dbeta, y_out, d_addend, dx);
-  MVK_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// ---- two BatchNorm problems of the same row count per launch (include/mvkpconv.h: mvk_bn_fwd_problem / _bwd_problem).
-// A bottleneck block normalises its convolution output and its shortcut (blocks.py:596-649) independently; issued as a
-// pair they cost one launch each way instead of two (three instead of five... for the two-launch backward of the big
-// levels). Problems that fall into different kernel families (row count, alignment) run one after the other.
-namespace {
-
+// kernel family of a problem: 0 = one workgroup per 64 channels (bn_small_*), 1 = register-resident float4 rows
+// (bn_mid_*), 2 = two-stage (partials, then finish + apply)
 int bn_family_fwd(const mvk_bn_fwd_problem& p) {
-  if (p.ext_rows < 0) return 2;          // finished statistics: the apply kernel alone
-  if (p.R <= bn_small_rows()) return 0;
-  if (p.R <= bn_mid_rows() && p.D % 4 == 0 &&
+  if (p.ext_rows < 0) return 2;          // finished statistics: the apply kernel alone, whatever the row count
+  if (p.R <= BN_SMALL_ROWS) return 0;
+  if (p.R <= BN_MID_ROWS && p.D % 4 == 0 &&
       aligned16(p.x, p.y, p.addend, p.gamma, p.beta, p.mean, p.invstd, p.running_mean) &&
       aligned16(p.running_var, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
     return 1;
@@ -1185,111 +776,125 @@ int bn_family_fwd(const mvk_bn_fwd_problem& p) {
 }
 
 int bn_family_bwd(const mvk_bn_bwd_problem& p) {
-  if (p.R <= bn_small_rows()) return 0;
-  if (p.R <= bn_mid_rows() && p.D % 4 == 0 &&
+  if (p.R <= BN_SMALL_ROWS) return 0;
+  if (p.R <= BN_MID_ROWS && p.D % 4 == 0 &&
       aligned16(p.x, p.g, p.y_out, p.d_addend, p.dgamma_dbeta, p.dx, p.mean, p.invstd) &&
       aligned16(p.gamma, p.beta, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
     return 1;
   return 2;
 }
 
-int bn_fwd_single(const mvk_bn_fwd_problem& p, void* stream) {
-  return mvk_bn_lrelu_fwd(p.x, p.n_valid, p.R, p.D, p.gamma, p.beta, p.eps, p.momentum, p.slope, p.running_mean,
-                          p.running_var, p.mean, p.invstd, p.scratch2D, p.y, p.num_batches_tracked, p.addend, p.ext_part,
-                          p.ext_rows, stream);
+// NP problems of the same row count and family as one launch (before it, one bn_stats_partial per two-stage problem that
+// brings no statistics partials)
+template <int NP>
+int bn_fwd_launch(const mvk_bn_fwd_problem* const* ps, void* stream) {
+  bn_fwd_problems<NP> a;
+  int Dm = 0;
+  for (int i = 0; i < NP; ++i) {
+    const mvk_bn_fwd_problem& p = a.p[i] = *ps[i];
+    MVK_REQUIRE(p.R >= 0 && p.D > 0 && p.R < (1ll << 31), "bn: bad sizes");
+    MVK_REQUIRE((p.ext_part == nullptr) == (p.ext_rows <= 0) && p.ext_rows >= -1,
+                "bn: ext_part and ext_rows go together (-1: finished statistics)");
+    Dm = p.D > Dm ? p.D : Dm;
+  }
+  const int R = (int)a.p[0].R;
+  if (R == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const int fam = bn_family_fwd(a.p[0]);
+  if (fam == 0) {
+    hipLaunchKernelGGL(bn_small_fwd<NP>, dim3((unsigned)cdiv64(Dm, 64), 1, NP), dim3(1024), 0, st, a);
+  } else if (fam == 1) {
+    hipLaunchKernelGGL(bn_mid_fwd<NP>, dim3((unsigned)cdiv64(Dm, 16), 1, NP), dim3(1024), 0, st, a);
+  } else {
+    const unsigned gyr = (unsigned)cdiv64(R, BN_ROWS);
+    for (mvk_bn_fwd_problem& p : a.p)
+      if (p.ext_rows == 0) {       // no statistics from the producing GEMM's epilogue: its own pass
+        hipLaunchKernelGGL(bn_stats_partial, dim3((unsigned)cdiv64(p.D, 64), gyr), dim3(BN_T), 0, st, p.x, p.n_valid, R, p.D,
+                           p.scratch2D);
+        p.ext_part = p.scratch2D;
+      }
+    const unsigned gy = gyr < (unsigned)BN_FUSED_GY ? gyr : (unsigned)BN_FUSED_GY;
+    hipLaunchKernelGGL(bn_finish_apply<NP>, dim3((unsigned)cdiv64(Dm, 64), gy, NP), dim3(1024), 0, st, a);
+  }
+  MVK_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
-int bn_bwd_single(const mvk_bn_bwd_problem& p, void* stream) {
-  return mvk_bn_lrelu_bwd(p.x, p.g, p.n_valid, p.R, p.D, p.gamma, p.beta, p.mean, p.invstd, p.slope, p.scratch,
-                          p.dgamma_dbeta, p.dx, p.y_out, p.d_addend, stream);
+template <int NP>
+int bn_bwd_launch(const mvk_bn_bwd_problem* const* ps, void* stream) {
+  bn_bwd_problems<NP> a;
+  int Dm = 0;
+  for (int i = 0; i < NP; ++i) {
+    const mvk_bn_bwd_problem& p = a.p[i] = *ps[i];
+    MVK_REQUIRE(p.R >= 0 && p.D > 0 && p.R < (1ll << 31), "bn: bad sizes");
+    MVK_REQUIRE((p.y_out == nullptr) == (p.d_addend == nullptr), "bn: y_out and d_addend go together (residual-join mode)");
+    Dm = p.D > Dm ? p.D : Dm;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int R = (int)a.p[0].R;
+  if (R == 0) {
+    for (const mvk_bn_bwd_problem& p : a.p) MVK_CHECK_HIP(hipMemsetAsync(p.dgamma_dbeta, 0, sizeof(float) * 2 * p.D, st));
+    return 0;
+  }
+  const int fam = bn_family_bwd(a.p[0]);
+  if (fam == 0) {
+    hipLaunchKernelGGL(bn_small_bwd<NP>, dim3((unsigned)cdiv64(Dm, 64), 1, NP), dim3(1024), 0, st, a);
+  } else if (fam == 1) {
+    hipLaunchKernelGGL(bn_mid_bwd<NP>, dim3((unsigned)cdiv64(Dm, 16), 1, NP), dim3(1024), 0, st, a);
+  } else {
+    const unsigned gyr = (unsigned)cdiv64(R, BN_ROWS);
+    hipLaunchKernelGGL(bn_bwd_reduce<NP>, dim3((unsigned)cdiv64(Dm, 64), gyr, NP), dim3(BN_T), 0, st, a);
+    const unsigned gy = gyr < (unsigned)BN_FUSED_GY ? gyr : (unsigned)BN_FUSED_GY;
+    hipLaunchKernelGGL(bn_bwd_finish_apply<NP>, dim3((unsigned)cdiv64(Dm, 64), gy, NP), dim3(1024), 0, st, a);
+  }
+  MVK_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
 }  // namespace
 
+// rows up to which mvk_bn_lrelu_fwd / _bwd are ONE launch for a D-channel input (a producer need not emit statistics)
+extern "C" int mvk_bn_single_launch_rows(int D) { return D % 4 == 0 ? BN_MID_ROWS : BN_SMALL_ROWS; }
+
+extern "C" int mvk_bn_lrelu_fwd(const float* x, const int32_t* n_valid, int64_t R, int D, const float* gamma,
+                                const float* beta, float eps, float momentum, float slope, float* running_mean,
+                                float* running_var, float* mean, float* invstd, float* scratch2D /* [ceil(R/64),2,D] */, float* y,
+                                int64_t* num_batches_tracked, const float* addend, const float* ext_part, int ext_rows,
+                                void* stream) {
+  const mvk_bn_fwd_problem p{x, n_valid, R, D, gamma, beta, eps, momentum, slope, running_mean, running_var, mean, invstd,
+                             scratch2D, y, num_batches_tracked, addend, ext_part, ext_rows};
+  const mvk_bn_fwd_problem* ps[1] = {&p};
+  return bn_fwd_launch<1>(ps, stream);
+}
+
+extern "C" int mvk_bn_lrelu_bwd(const float* x, const float* g, const int32_t* n_valid, int64_t R, int D,
+                                const float* gamma, const float* beta, const float* mean, const float* invstd,
+                                float slope, float* scratch /* [ceil(R/64),2,D] */,
+                                float* dgamma_dbeta /* [2,D]: dbeta then dgamma */, float* dx, const float* y_out,
+                                float* d_addend, void* stream) {
+  const mvk_bn_bwd_problem p{x, g, n_valid, R, D, gamma, beta, mean, invstd, slope, scratch, dgamma_dbeta, dx, y_out, d_addend};
+  const mvk_bn_bwd_problem* ps[1] = {&p};
+  return bn_bwd_launch<1>(ps, stream);
+}
+
+// ---- two BatchNorm problems of the same row count per launch. A bottleneck block normalises its convolution output and
+// its shortcut (blocks.py:596-649) independently; issued as a pair they cost one launch each way instead of two (two
+// instead of four for the two-stage backward of the big levels). Problems that fall into different kernel families
+// (row count, alignment) or differ in rows run one after the other.
 extern "C" int mvk_bn_lrelu_fwd_pair(const mvk_bn_fwd_problem* pa, const mvk_bn_fwd_problem* pb, void* stream) {
   MVK_REQUIRE(pa && pb, "bn pair: null problem");
-  const mvk_bn_fwd_problem &a = *pa, &b = *pb;
-  const int fam = bn_family_fwd(a);
-  if (a.R != b.R || a.R <= 0 || fam != bn_family_fwd(b) || (fam == 2 && !bn_fused_finish())) {
-    if (int e = bn_fwd_single(a, stream)) return e;
-    return bn_fwd_single(b, stream);
-  }
-  MVK_REQUIRE(a.D > 0 && b.D > 0 && a.R < (1ll << 31), "bn: bad sizes");
-  MVK_REQUIRE((a.ext_part == nullptr) == (a.ext_rows <= 0) && (b.ext_part == nullptr) == (b.ext_rows <= 0) &&
-                  a.ext_rows >= -1 && b.ext_rows >= -1,
-              "bn: ext_part and ext_rows go together");
-  hipStream_t st = (hipStream_t)stream;
-  const int R = (int)a.R, Dm = a.D > b.D ? a.D : b.D;
-  if (fam == 0) {
-    bn_small_fwd_args k0{a.x, a.n_valid, R, a.D, a.gamma, a.beta, a.eps, a.momentum, a.slope, a.running_mean, a.running_var,
-                         a.mean, a.invstd, a.y, (long long*)a.num_batches_tracked, a.addend};
-    bn_small_fwd_args k1{b.x, b.n_valid, R, b.D, b.gamma, b.beta, b.eps, b.momentum, b.slope, b.running_mean, b.running_var,
-                         b.mean, b.invstd, b.y, (long long*)b.num_batches_tracked, b.addend};
-    hipLaunchKernelGGL(bn_small_fwd_pair, dim3((unsigned)cdiv64(Dm, 64), 1, 2), dim3(1024), 0, st, k0, k1);
-  } else if (fam == 1) {
-    bn_mid_fwd_args k0{a.x, a.n_valid, R, a.D, a.gamma, a.beta, a.eps, a.momentum, a.slope, a.running_mean, a.running_var,
-                       a.mean, a.invstd, a.y, (long long*)a.num_batches_tracked, a.addend};
-    bn_mid_fwd_args k1{b.x, b.n_valid, R, b.D, b.gamma, b.beta, b.eps, b.momentum, b.slope, b.running_mean, b.running_var,
-                       b.mean, b.invstd, b.y, (long long*)b.num_batches_tracked, b.addend};
-    hipLaunchKernelGGL(bn_mid_fwd_pair, dim3((unsigned)cdiv64(Dm, 16), 1, 2), dim3(1024), 0, st, k0, k1);
-  } else {
-    const unsigned gyr = (unsigned)cdiv64(R, BN_ROWS);
-    for (const mvk_bn_fwd_problem* p : {pa, pb})
-      if (p->ext_part == nullptr && p->ext_rows == 0)       // no statistics from the producing GEMM (a split reduction): its own pass
-        hipLaunchKernelGGL(bn_stats_partial, dim3((unsigned)cdiv64(p->D, 64), gyr), dim3(BN_T), 0, st, p->x, p->n_valid, R,
-                           p->D, p->scratch2D);
-    const unsigned gy = gyr < (unsigned)bn_fused_gy() ? gyr : (unsigned)bn_fused_gy();
-    bn_finish_apply_args k0{a.x, a.n_valid, R, a.D, a.ext_part ? a.ext_part : a.scratch2D, a.eps, a.momentum, a.gamma, a.beta,
-                            a.slope, a.mean, a.invstd, a.running_mean, a.running_var, (long long*)a.num_batches_tracked,
-                            a.addend, a.y, a.ext_rows};
-    bn_finish_apply_args k1{b.x, b.n_valid, R, b.D, b.ext_part ? b.ext_part : b.scratch2D, b.eps, b.momentum, b.gamma, b.beta,
-                            b.slope, b.mean, b.invstd, b.running_mean, b.running_var, (long long*)b.num_batches_tracked,
-                            b.addend, b.y, b.ext_rows};
-    hipLaunchKernelGGL(bn_finish_apply_pair, dim3((unsigned)cdiv64(Dm, 64), gy, 2), dim3(1024), 0, st, k0, k1);
-  }
-  MVK_CHECK_HIP(hipGetLastError());
-  return 0;
+  const mvk_bn_fwd_problem* ps[2] = {pa, pb};
+  if (pa->R == pb->R && pa->R > 0 && bn_family_fwd(*pa) == bn_family_fwd(*pb)) return bn_fwd_launch<2>(ps, stream);
+  if (int e = bn_fwd_launch<1>(ps, stream)) return e;
+  return bn_fwd_launch<1>(ps + 1, stream);
 }
 
 extern "C" int mvk_bn_lrelu_bwd_pair(const mvk_bn_bwd_problem* pa, const mvk_bn_bwd_problem* pb, void* stream) {
   MVK_REQUIRE(pa && pb, "bn pair: null problem");
-  const mvk_bn_bwd_problem &a = *pa, &b = *pb;
-  const int fam = bn_family_bwd(a);
-  if (a.R != b.R || a.R <= 0 || fam != bn_family_bwd(b) || (fam == 2 && !bn_fused_finish())) {
-    if (int e = bn_bwd_single(a, stream)) return e;
-    return bn_bwd_single(b, stream);
-  }
-  MVK_REQUIRE(a.D > 0 && b.D > 0 && a.R < (1ll << 31), "bn: bad sizes");
-  MVK_REQUIRE((a.y_out == nullptr) == (a.d_addend == nullptr) && (b.y_out == nullptr) == (b.d_addend == nullptr),
-              "bn: y_out and d_addend go together (residual-join mode)");
-  hipStream_t st = (hipStream_t)stream;
-  const int R = (int)a.R, Dm = a.D > b.D ? a.D : b.D;
-  if (fam == 0) {
-    bn_small_bwd_args k0{a.x, a.g, a.n_valid, R, a.D, a.mean, a.invstd, a.gamma, a.beta, a.slope, a.y_out, a.d_addend,
-                         a.dgamma_dbeta, a.dx};
-    bn_small_bwd_args k1{b.x, b.g, b.n_valid, R, b.D, b.mean, b.invstd, b.gamma, b.beta, b.slope, b.y_out, b.d_addend,
-                         b.dgamma_dbeta, b.dx};
-    hipLaunchKernelGGL(bn_small_bwd_pair, dim3((unsigned)cdiv64(Dm, 64), 1, 2), dim3(1024), 0, st, k0, k1);
-  } else if (fam == 1) {
-    bn_mid_bwd_args k0{a.x, a.g, a.n_valid, R, a.D, a.mean, a.invstd, a.gamma, a.beta, a.slope, a.y_out, a.d_addend,
-                       a.dgamma_dbeta, a.dx};
-    bn_mid_bwd_args k1{b.x, b.g, b.n_valid, R, b.D, b.mean, b.invstd, b.gamma, b.beta, b.slope, b.y_out, b.d_addend,
-                       b.dgamma_dbeta, b.dx};
-    hipLaunchKernelGGL(bn_mid_bwd_pair, dim3((unsigned)cdiv64(Dm, 16), 1, 2), dim3(1024), 0, st, k0, k1);
-  } else {
-    const unsigned gyr = (unsigned)cdiv64(R, BN_ROWS);
-    bn_bwd_reduce_args r0{a.x, a.g, a.n_valid, R, a.D, a.mean, a.invstd, a.gamma, a.beta, a.slope, a.y_out, a.scratch};
-    bn_bwd_reduce_args r1{b.x, b.g, b.n_valid, R, b.D, b.mean, b.invstd, b.gamma, b.beta, b.slope, b.y_out, b.scratch};
-    hipLaunchKernelGGL(bn_bwd_reduce_pair, dim3((unsigned)cdiv64(Dm, 64), gyr, 2), dim3(BN_T), 0, st, r0, r1);
-    const unsigned gy = gyr < (unsigned)bn_fused_gy() ? gyr : (unsigned)bn_fused_gy();
-    bn_bwd_finish_apply_args k0{a.x, a.g, a.n_valid, R, a.D, a.mean, a.invstd, a.gamma, a.beta, a.slope, a.scratch, a.y_out,
-                                a.d_addend, a.dgamma_dbeta, a.dx};
-    bn_bwd_finish_apply_args k1{b.x, b.g, b.n_valid, R, b.D, b.mean, b.invstd, b.gamma, b.beta, b.slope, b.scratch, b.y_out,
-                                b.d_addend, b.dgamma_dbeta, b.dx};
-    hipLaunchKernelGGL(bn_bwd_finish_apply_pair, dim3((unsigned)cdiv64(Dm, 64), gy, 2), dim3(1024), 0, st, k0, k1);
-  }
-  MVK_CHECK_HIP(hipGetLastError());
-  return 0;
+  const mvk_bn_bwd_problem* ps[2] = {pa, pb};
+  if (pa->R == pb->R && pa->R > 0 && bn_family_bwd(*pa) == bn_family_bwd(*pb)) return bn_bwd_launch<2>(ps, stream);
+  if (int e = bn_bwd_launch<1>(ps, stream)) return e;
+  return bn_bwd_launch<1>(ps + 1, stream);
 }
 
 // ---- bias + LeakyReLU of the layers without BatchNorm (blocks.py:462-463 `x + self.bias`, then the block's

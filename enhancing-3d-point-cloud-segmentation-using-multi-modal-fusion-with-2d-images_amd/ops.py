@@ -1109,6 +1109,46 @@ def _ext3(ext):
     return (ext[0], ext[1], ext[2] if len(ext) > 2 else None)
 
 
+def _bn_fwd_problem(who, x, n_valid, gamma, beta, running_mean, running_var, cfg, nbt, addend, ext):
+    """The arguments of mvk_bn_lrelu_fwd for x [R,D] (f32, contiguous) in the order of the export and of the fields of
+    mvk_bn_fwd_problem, cfg = (eps, momentum, slope), ext = the input's `_mvk_bn_stats` record; then y, mean, invstd and
+    whatever else must stay alive until the launch has been issued."""
+    R, D = x.shape
+    y = torch.empty_like(x)
+    ext_part, ext_rows, fin = _ext3(ext)
+    if ext_part is not None and (ext_part.shape[2] != D or ext_part.shape[0] != (R + ext_rows - 1) // ext_rows):
+        raise RuntimeError("%s: the statistics partials do not belong to this tensor" % who)
+    scratch = None
+    if fin is not None:
+        # statistics finished by the producing product (mean, invstd, running statistics, batch counter): apply only
+        mean, invstd = fin
+        running_mean = running_var = nbt = ext_part = None
+        ext_rows = -1
+    else:
+        mean = torch.empty(D, device=x.device, dtype=torch.float32)
+        invstd = torch.empty(D, device=x.device, dtype=torch.float32)
+        if ext_part is None:
+            scratch = torch.empty(((R + 63) // 64) * 2 * D, device=x.device, dtype=torch.float32)
+    eps, momentum, slope = cfg
+    args = (_p(x), _p(n_valid), R, D, _p(gamma), _p(beta), float(eps), float(momentum), float(slope), _p(running_mean),
+            _p(running_var), _p(mean), _p(invstd), _p(scratch), _p(y), _p(nbt), _p(addend), _p(ext_part), int(ext_rows))
+    return args, y, mean, invstd, scratch
+
+
+def _bn_bwd_problem(x, g, n_valid, gamma, beta, mean, invstd, slope, yout):
+    """The arguments of mvk_bn_lrelu_bwd (= the fields of mvk_bn_bwd_problem) for the upstream gradient g; then
+    dgamma_dbeta [2D] (dbeta, then dgamma), dx, the addend's gradient (None without yout) and what must stay alive."""
+    g = _f32c(g)
+    R, D = x.shape
+    dgb = torch.empty(2 * D, device=x.device, dtype=torch.float32)
+    scratch = torch.empty(((R + 63) // 64) * 2 * D, device=x.device, dtype=torch.float32)
+    dx = torch.empty_like(x)
+    d_add = torch.empty_like(x) if yout is not None else None
+    args = (_p(x), _p(g), _p(n_valid), R, D, _p(gamma), _p(beta), _p(mean), _p(invstd), float(slope), _p(scratch), _p(dgb),
+            _p(dx), _p(yout), _p(d_add))
+    return args, dgb, dx, d_add, (g, scratch)
+
+
 class _BNLReLUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, n_valid, gamma, beta, running_mean, running_var, eps, momentum, slope, training, nbt=None,
@@ -1119,27 +1159,11 @@ class _BNLReLUFn(torch.autograd.Function):
             addend = _f32c(addend)
             if addend.shape != x.shape:
                 raise RuntimeError("bn_lrelu: the residual addend must have the shape of the input")
-        R, D = x.shape
-        y = torch.empty_like(x)
-        mean = torch.empty(D, device=x.device, dtype=torch.float32)
-        invstd = torch.empty(D, device=x.device, dtype=torch.float32)
         if not training:
             raise RuntimeError("masked BatchNorm is a training-mode op; use nn.BatchNorm1d in eval mode")
-        ext_part, ext_rows, fin = _ext3(ext)
-        if ext_part is not None and (ext_part.shape[2] != D or ext_part.shape[0] != (R + ext_rows - 1) // ext_rows):
-            raise RuntimeError("bn_lrelu: the statistics partials do not belong to this tensor")
-        if fin is not None:
-            # statistics finished by the producing product (mean, invstd, running statistics, batch counter): apply only
-            mean, invstd = fin
-            check(lib().mvk_bn_lrelu_fwd(_p(x), _p(n_valid), R, D, _p(gamma), _p(beta), float(eps), float(momentum),
-                                         float(slope), None, None, _p(mean), _p(invstd), None, _p(y), None, _p(addend),
-                                         None, -1, _stream()))
-        else:
-            scratch = None if ext_part is not None else torch.empty(((R + 63) // 64) * 2 * D, device=x.device,
-                                                                    dtype=torch.float32)
-            check(lib().mvk_bn_lrelu_fwd(_p(x), _p(n_valid), R, D, _p(gamma), _p(beta), float(eps), float(momentum),
-                                         float(slope), _p(running_mean), _p(running_var), _p(mean), _p(invstd),
-                                         _p(scratch), _p(y), _p(nbt), _p(addend), _p(ext_part), int(ext_rows), _stream()))
+        args, y, mean, invstd, _keep = _bn_fwd_problem("bn_lrelu", x, n_valid, gamma, beta, running_mean, running_var,
+                                                       (eps, momentum, slope), nbt, addend, ext)
+        check(lib().mvk_bn_lrelu_fwd(*args, _stream()))
         ctx.save_for_backward(x, n_valid, gamma, beta, mean, invstd, y if addend is not None else None)
         ctx.slope = float(slope)
         return y
@@ -1147,14 +1171,9 @@ class _BNLReLUFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, n_valid, gamma, beta, mean, invstd, yout = ctx.saved_tensors
-        g = _f32c(g)
-        R, D = x.shape
-        dgb = torch.empty(2 * D, device=x.device, dtype=torch.float32)
-        scratch = torch.empty(((R + 63) // 64) * 2 * D, device=x.device, dtype=torch.float32)
-        dx = torch.empty_like(x)
-        d_add = torch.empty_like(x) if yout is not None else None
-        check(lib().mvk_bn_lrelu_bwd(_p(x), _p(g), _p(n_valid), R, D, _p(gamma), _p(beta), _p(mean), _p(invstd),
-                                     ctx.slope, _p(scratch), _p(dgb), _p(dx), _p(yout), _p(d_add), _stream()))
+        args, dgb, dx, d_add, _keep = _bn_bwd_problem(x, g, n_valid, gamma, beta, mean, invstd, ctx.slope, yout)
+        check(lib().mvk_bn_lrelu_bwd(*args, _stream()))
+        D = x.shape[1]
         return dx, None, dgb[D:], dgb[:D], None, None, None, None, None, None, None, d_add, None
 
 
@@ -1231,13 +1250,9 @@ class _BNLazyFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, n_valid, gamma, beta, mean, invstd = ctx.saved_tensors
-        g = _f32c(g)
-        R, D = x.shape
-        dgb = torch.empty(2 * D, device=x.device, dtype=torch.float32)
-        scratch = torch.empty(((R + 63) // 64) * 2 * D, device=x.device, dtype=torch.float32)
-        dx = torch.empty_like(x)
-        check(lib().mvk_bn_lrelu_bwd(_p(x), _p(g), _p(n_valid), R, D, _p(gamma), _p(beta), _p(mean), _p(invstd),
-                                     ctx.slope, _p(scratch), _p(dgb), _p(dx), None, None, _stream()))
+        args, dgb, dx, _, _keep = _bn_bwd_problem(x, g, n_valid, gamma, beta, mean, invstd, ctx.slope, None)
+        check(lib().mvk_bn_lrelu_bwd(*args, _stream()))
+        D = x.shape[1]
         return dx, None, dgb[D:], dgb[:D], None, None, None
 
 
@@ -1281,55 +1296,25 @@ class _BNLReLUPairFn(torch.autograd.Function):
         xa, xb = _f32c(xa), _f32c(xb)
         if xa.shape[0] != xb.shape[0]:
             raise RuntimeError("bn_lrelu_pair: the two inputs differ in rows")
-        R = xa.shape[0]
-        probs, keep = [], []
-        for x, g, b, rm, rv, (eps, mom, slope), nbt, ext in ((xa, ga, ba, rma, rva, cfg_a, nbt_a, ext_a),
-                                                              (xb, gb, bb, rmb, rvb, cfg_b, nbt_b, ext_b)):
-            D = x.shape[1]
-            y = torch.empty_like(x)
-            mean = torch.empty(D, device=x.device, dtype=torch.float32)
-            invstd = torch.empty(D, device=x.device, dtype=torch.float32)
-            ext_part, ext_rows, fin = _ext3(ext)
-            if ext_part is not None and (ext_part.shape[2] != D or ext_part.shape[0] != (R + ext_rows - 1) // ext_rows):
-                raise RuntimeError("bn_lrelu_pair: the statistics partials do not belong to this tensor")
-            if fin is not None:       # finished by the producing product: apply only (see _BNLReLUFn)
-                mean, invstd = fin
-                scratch = None
-                probs.append(BnFwdProblem(_p(x), _p(n_valid), R, D, _p(g), _p(b), float(eps), float(mom), float(slope), None,
-                                          None, _p(mean), _p(invstd), None, _p(y), None, None, None, -1))
-                keep.append((y, mean, invstd, scratch))
-                continue
-            scratch = None if ext_part is not None else torch.empty(((R + 63) // 64) * 2 * D, device=x.device,
-                                                                    dtype=torch.float32)
-            probs.append(BnFwdProblem(_p(x), _p(n_valid), R, D, _p(g), _p(b), float(eps), float(mom), float(slope), _p(rm),
-                                      _p(rv), _p(mean), _p(invstd), _p(scratch), _p(y), _p(nbt), None, _p(ext_part),
-                                      int(ext_rows)))
-            keep.append((y, mean, invstd, scratch))
-        check(lib().mvk_bn_lrelu_fwd_pair(C.byref(probs[0]), C.byref(probs[1]), _stream()))
-        ctx.save_for_backward(xa, xb, n_valid, ga, ba, gb, bb, keep[0][1], keep[0][2], keep[1][1], keep[1][2])
+        (args_a, ya, mean_a, is_a, _ka), (args_b, yb, mean_b, is_b, _kb) = [
+            _bn_fwd_problem("bn_lrelu_pair", x, n_valid, g, b, rm, rv, cfg, nbt, None, ext)
+            for x, g, b, rm, rv, cfg, nbt, ext in ((xa, ga, ba, rma, rva, cfg_a, nbt_a, ext_a),
+                                                   (xb, gb, bb, rmb, rvb, cfg_b, nbt_b, ext_b))]
+        check(lib().mvk_bn_lrelu_fwd_pair(C.byref(BnFwdProblem(*args_a)), C.byref(BnFwdProblem(*args_b)), _stream()))
+        ctx.save_for_backward(xa, xb, n_valid, ga, ba, gb, bb, mean_a, is_a, mean_b, is_b)
         ctx.slopes = (float(cfg_a[2]), float(cfg_b[2]))
         ctx.set_materialize_grads(False)
-        return keep[0][0], keep[1][0]
+        return ya, yb
 
     @staticmethod
     def backward(ctx, g_a, g_b):
         from ._lib import BnBwdProblem
         xa, xb, n_valid, ga, ba, gb, bb, mean_a, is_a, mean_b, is_b = ctx.saved_tensors
-        R = xa.shape[0]
-        sets = []
-        for x, g, gam, bet, mean, istd, slope in ((xa, g_a, ga, ba, mean_a, is_a, ctx.slopes[0]),
-                                                  (xb, g_b, gb, bb, mean_b, is_b, ctx.slopes[1])):
-            if g is None:
-                g = torch.zeros_like(x)
-            g = _f32c(g)
-            D = x.shape[1]
-            dgb = torch.empty(2 * D, device=x.device, dtype=torch.float32)
-            scratch = torch.empty(((R + 63) // 64) * 2 * D, device=x.device, dtype=torch.float32)
-            dx = torch.empty_like(x)
-            sets.append((BnBwdProblem(_p(x), _p(g), _p(n_valid), R, D, _p(gam), _p(bet), _p(mean), _p(istd), float(slope),
-                                      _p(scratch), _p(dgb), _p(dx), None, None), dgb, dx, g, scratch))
-        check(lib().mvk_bn_lrelu_bwd_pair(C.byref(sets[0][0]), C.byref(sets[1][0]), _stream()))
-        (_, dgb_a, dx_a, _, _), (_, dgb_b, dx_b, _, _) = sets
+        (args_a, dgb_a, dx_a, _, _ka), (args_b, dgb_b, dx_b, _, _kb) = [
+            _bn_bwd_problem(x, g if g is not None else torch.zeros_like(x), n_valid, gam, bet, mean, istd, slope, None)
+            for x, g, gam, bet, mean, istd, slope in ((xa, g_a, ga, ba, mean_a, is_a, ctx.slopes[0]),
+                                                      (xb, g_b, gb, bb, mean_b, is_b, ctx.slopes[1]))]
+        check(lib().mvk_bn_lrelu_bwd_pair(C.byref(BnBwdProblem(*args_a)), C.byref(BnBwdProblem(*args_b)), _stream()))
         Da, Db = xa.shape[1], xb.shape[1]
         return (dx_a, dx_b, None, dgb_a[Da:], dgb_a[:Da], None, None, dgb_b[Db:], dgb_b[:Db], None, None, None, None, None,
                 None, None, None)

@@ -513,6 +513,50 @@ def test_bn_lrelu_pair_equals_two_single_launches(ops, R, Da, Db, from_gemm):
         assert torch.equal(m1.weight.grad, m2.weight.grad) and torch.equal(m1.bias.grad, m2.bias.grad)
 
 
+def off_by_one_float(t):
+    """A contiguous copy of t whose storage starts one float past a 16-byte boundary."""
+    buf = torch.empty(t.numel() + 1, device=t.device, dtype=t.dtype)
+    v = buf[1:].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 == 4 and v.is_contiguous()
+    return v
+
+
+def test_bn_lrelu_pair_with_one_misaligned_problem_equals_two_single_launches(ops):
+    """Two problems of 300 rows (the register-resident family) whose second input, and its upstream gradient, start one
+    float past a 16-byte boundary: that problem cannot take the float4 kernels, the two fall into different families
+    and the pair runs as two single dispatches -- still bit-identical to two calls of bn_lrelu."""
+    R, Da, Db = 300, 64, 128
+    rng = np.random.default_rng(R + Da)
+    n_valid = T(np.asarray([R - 37], np.int32))
+    Xa, Xb = T(rng.normal(size=(R, Da)).astype(np.float32)), T(rng.normal(size=(R, Db)).astype(np.float32) * 3 + 1)
+    ga, gb = T(rng.normal(size=(R, Da)).astype(np.float32)), off_by_one_float(T(rng.normal(size=(R, Db)).astype(np.float32)))
+
+    def make():
+        torch.manual_seed(1)
+        bns = [torch.nn.BatchNorm1d(D, momentum=0.02).cuda().train() for D in (Da, Db)]
+        for bn in bns:
+            bn.weight.data.uniform_(0.5, 1.5)
+            bn.bias.data.uniform_(-0.3, 0.3)
+        return bns
+
+    bn1 = make()
+    xa, xb = Xa.clone().requires_grad_(True), off_by_one_float(Xb).requires_grad_(True)
+    ya = ops.bn_lrelu(xa, n_valid, bn1[0], 0.1)
+    yb = ops.bn_lrelu(xb, n_valid, bn1[1], 1.0)
+    torch.autograd.backward([ya, yb], [ga, gb])
+    bn2 = make()
+    pa, pb = Xa.clone().requires_grad_(True), off_by_one_float(Xb).requires_grad_(True)
+    za, zb = ops.bn_lrelu_pair(pa, bn2[0], 0.1, pb, bn2[1], 1.0, n_valid)
+    torch.autograd.backward([za, zb], [ga, gb])
+    assert torch.equal(za, ya) and torch.equal(zb, yb) and (zb[R - 37:] == 0).all()
+    assert torch.equal(pa.grad, xa.grad) and torch.equal(pb.grad, xb.grad)
+    for m1, m2 in zip(bn1, bn2):
+        assert torch.equal(m1.running_mean, m2.running_mean) and torch.equal(m1.running_var, m2.running_var)
+        assert int(m1.num_batches_tracked) == int(m2.num_batches_tracked) == 1
+        assert torch.equal(m1.weight.grad, m2.weight.grad) and torch.equal(m1.bias.grad, m2.bias.grad)
+
+
 @pytest.mark.parametrize("M,Kd,N0,N1,stats", [(4288, 128, 64, 256, True), (332, 512, 256, 1024, False),
                                               (85, 1024, 512, 2048, False), (19464, 64, 32, 128, True), (1300, 256, 128, 512, True)])
 def test_linear_pair_equals_two_linear_layers(ops, M, Kd, N0, N1, stats):
@@ -1413,6 +1457,48 @@ def test_masked_bn_with_residual_join_vs_torch(ops, R, D, n):
     assert rel_err((gs[:n] * away).cpu().numpy(), (gsr * away).cpu().numpy()) < 1e-6
     assert rel_err((gx[:n] * away).cpu().numpy(), (gxr * away).cpu().numpy()) < 1e-2
     assert rel_err(gw.cpu().numpy(), gwr.cpu().numpy()) < 1e-2 and rel_err(gb.cpu().numpy(), gbr.cpu().numpy()) < 1e-2
+
+
+@pytest.mark.parametrize("slope", [1.0, 0.1])
+@pytest.mark.parametrize("join", [False, True])
+def test_masked_bn_misaligned_base_takes_two_stage_kernels_vs_torch(ops, join, slope):
+    """300 rows x 64 channels is the register-resident family's shape, but input, shortcut and upstream gradient start
+    one float past a 16-byte boundary: the float4 kernels must not run, the two-stage ones do. Against torch under the
+    bounds of test_masked_bn_lrelu_vs_torch (the shortcut's gradient: the 1e-6 of the residual-join test)."""
+    R, D, n = 300, 64, 263
+    torch.manual_seed(R + D)
+    x = off_by_one_float(torch.randn(R, D, device="cuda") * 2 + 3).requires_grad_(True)
+    sc = off_by_one_float(torch.randn(R, D, device="cuda")).requires_grad_(True) if join else None
+    go = off_by_one_float(torch.randn(R, D, device="cuda"))
+    bn = torch.nn.BatchNorm1d(D, momentum=0.02).cuda()
+    with torch.no_grad():
+        bn.weight.uniform_(0.5, 1.5)
+        bn.bias.uniform_(-0.5, 0.5)
+    ref = torch.nn.BatchNorm1d(D, momentum=0.02).cuda()
+    ref.load_state_dict(bn.state_dict())
+    nv = torch.tensor([n], dtype=torch.int32, device="cuda")
+    leaves = [x, bn.weight, bn.bias] + ([sc] if join else [])
+    for _ in range(2):
+        y = ops.bn_lrelu(x, nv, bn, slope=slope, addend=sc)
+        gx, gw, gb, *gs = torch.autograd.grad(y, leaves, go)
+    xr = x.detach()[:n].clone().requires_grad_(True)
+    sr = sc.detach()[:n].clone().requires_grad_(True) if join else None
+    for _ in range(2):
+        yr = torch.nn.functional.leaky_relu(ref(xr) + sr if join else ref(xr), slope)
+        gxr, gwr, gbr, *gsr = torch.autograd.grad(yr, [xr, ref.weight, ref.bias] + ([sr] if join else []), go[:n])
+    assert (y[n:] == 0).all() and (gx[n:] == 0).all()
+    assert rel_err(y[:n].detach().cpu().numpy(), yr.detach().cpu().numpy()) < 1e-5
+    away = (yr.detach().abs() > 1e-4).float() if slope != 1.0 else torch.ones_like(yr)
+    assert away.mean() > 0.99
+    ptol = 1e-4 if slope == 1.0 else 1e-2
+    assert rel_err((gx[:n] * away).cpu().numpy(), (gxr * away).cpu().numpy()) < ptol
+    assert rel_err(gw.cpu().numpy(), gwr.cpu().numpy()) < ptol and rel_err(gb.cpu().numpy(), gbr.cpu().numpy()) < ptol
+    if join:
+        assert (gs[0][n:] == 0).all()
+        assert rel_err((gs[0][:n] * away).cpu().numpy(), (gsr[0] * away).cpu().numpy()) < 1e-6
+    assert rel_err(bn.running_mean.cpu().numpy(), ref.running_mean.cpu().numpy()) < 1e-5
+    assert rel_err(bn.running_var.cpu().numpy(), ref.running_var.cpu().numpy()) < 1e-5
+    assert int(bn.num_batches_tracked) == int(ref.num_batches_tracked) == 2
 
 
 # ------------------------------------------------------------------ fused clip + SGD
