@@ -31,6 +31,7 @@ SOURCES = [
     ("fusion.hip", ["-ffp-contract=off"]),
     ("vote.hip", ["-ffp-contract=off"]),      # float64 vote update in two roundings, like NumPy
     ("pn2.hip", ["-ffp-contract=off"]),       # squared distances in three rounded products and two rounded sums
+    ("chunk.hip", ["-ffp-contract=off"]),     # float64 box tests, float32 vote sums and division as NumPy evaluates them
 ]
 
 
@@ -50,7 +51,8 @@ def _stale(target, deps):
 
 def build_library(force=False, verbose=False):
     hipcc = _hipcc()
-    common = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "blockscan.h"), os.path.join(HERE, "..", "include", "mvkpconv.h"),
+    common = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "blockscan.h"), os.path.join(CSRC, "compact.h"),
+              os.path.join(HERE, "..", "include", "mvkpconv.h"),
               os.path.join(HERE, "..", "include", "mvk_prime_list.h"), os.path.abspath(__file__)]
     objs, jobs = [], []
     for src, extra in SOURCES:

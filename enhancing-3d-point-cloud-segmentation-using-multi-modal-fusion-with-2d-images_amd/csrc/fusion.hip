@@ -6,6 +6,7 @@
 // Compiled with -ffp-contract=off: the float64 products and sums are evaluated exactly in the
 // written order, like the NumPy / scikit-learn code they replace.
 #include "common.h"
+#include "compact.h"
 
 namespace {
 
@@ -609,28 +610,8 @@ __global__ __launch_bounds__(1024) void ball_count_kernel(const float* __restric
 __global__ __launch_bounds__(1024) void ball_scan_kernel(int* __restrict__ block_count, int nblk, int64_t* __restrict__ count) {
   __shared__ int carry;
   __shared__ int ws[16];
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < nblk; base += 1024) {
-    const int i = base + threadIdx.x;
-    const int v = i < nblk ? block_count[i] : 0;
-    int x = v;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      int y = __shfl_up(x, o);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) ws[w] = x;
-    __syncthreads();
-    int off = carry;
-    for (int k = 0; k < w; ++k) off += ws[k];
-    if (i < nblk) block_count[i] = off + x - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry = off + x;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *count = carry;
+  const int total = compact_scan_counts(block_count, nblk, &carry, ws);
+  if (threadIdx.x == 0) *count = total;
 }
 
 __global__ __launch_bounds__(1024) void ball_scatter_kernel(const float* __restrict__ pts, int64_t N, Ball b,
@@ -649,9 +630,7 @@ __global__ __launch_bounds__(1024) void ball_scatter_kernel(const float* __restr
   if (lane == 0) wc[w] = __popcll(m);
   __syncthreads();
   if (in) {
-    int off = block_off[blockIdx.x];
-    for (int k = 0; k < w; ++k) off += wc[k];
-    off += __popcll(m & ((1ull << lane) - 1ull));
+    const int off = block_off[blockIdx.x] + compact_wave_offset(wc, w) + compact_lane_rank(m);
     out_idx[off] = i;
     if (out_d2) out_d2[off] = d2;
   }

@@ -2708,3 +2708,122 @@ def affine_lrelu(x, scale, shift, slope=1.0, addend=None):
     check(lib().mvk_affine_lrelu(_p(x), _p(scale), _p(shift), _p(addend), x.shape[0], x.shape[1], float(slope), _p(y),
                                  _stream()))
     return y
+
+
+# --------------------------------------------------------------------------------------------
+# MVPNet whole-scene test: chunk boxes, logit votes, confusion (csrc/chunk.hip); forward only
+# --------------------------------------------------------------------------------------------
+
+def _boxes_dev(boxes, device):
+    b = _np.ascontiguousarray(_np.asarray(boxes, dtype=_np.float64).reshape(-1, 4))
+    return torch.from_numpy(b).to(device), b.shape[0]
+
+
+def box_count(points, boxes):
+    """counts [n] int64 (HBM): the points of `points` [N,3] f32 (HBM) inside each of the n xy boxes, `boxes` a HOST
+    float64 array [n,4] (x_lo, y_lo, x_hi, y_hi). Both ends inclusive, compared in float64 (chunk_util.py:39,43). One
+    launch for all boxes; nothing comes back to the host."""
+    _dev(points)
+    pts = _f32c(points)
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise RuntimeError("box_count: points [N,3] expected")
+    bx, n = _boxes_dev(boxes, pts.device)
+    counts = torch.empty((n,), device=pts.device, dtype=torch.int64)
+    check(lib().mvk_box_count(_p(pts), pts.shape[0], _p(bx), n, _p(counts), _stream()))
+    return counts
+
+
+def box_select(points, boxes, counts_host, with_z=True):
+    """The members of every box in ascending order as one CSR: (offsets [n+1] int64, idx [total] int64, zmin [n] f32,
+    zmax [n] f32), all in HBM (zmin / zmax None without with_z). counts_host: the n counts that box_count gave for these
+    boxes, on the HOST (the caller has read them to choose the boxes); they size the result, so nothing is read back."""
+    _dev(points)
+    pts = _f32c(points)
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise RuntimeError("box_select: points [N,3] expected")
+    bx, n = _boxes_dev(boxes, pts.device)
+    cnt = _np.asarray(counts_host, dtype=_np.int64).reshape(-1)
+    if cnt.shape[0] != n or (cnt < 0).any():
+        raise RuntimeError("box_select: one non-negative count per box expected")
+    off_host = _np.zeros(n + 1, _np.int64)
+    _np.cumsum(cnt, out=off_host[1:])
+    total = int(off_host[-1])
+    offsets = torch.from_numpy(off_host).to(pts.device)
+    idx = torch.empty((total,), device=pts.device, dtype=torch.int64)
+    zmin = torch.empty((n,), device=pts.device, dtype=torch.float32) if with_z else None
+    zmax = torch.empty((n,), device=pts.device, dtype=torch.float32) if with_z else None
+    ws = _workspace("box_select", lib().mvk_box_select_workspace(pts.shape[0], n), pts.device)
+    check(lib().mvk_box_select(_p(pts), pts.shape[0], _p(bx), n, _p(offsets), total, _p(idx), _p(zmin), _p(zmax), _p(ws),
+                               ws.numel(), _stream()))
+    return offsets, idx, zmin, zmax
+
+
+def _vote_state(sums, counts):
+    if sums.dtype != torch.float32 or sums.dim() != 2 or not sums.is_contiguous():
+        raise RuntimeError("chunk vote: sums must be a contiguous float32 [N, C] tensor")
+    if counts.dtype != torch.int32 or counts.shape != (sums.shape[0],) or not counts.is_contiguous():
+        raise RuntimeError("chunk vote: counts must be a contiguous int32 [N] tensor")
+
+
+def chunk_vote_add(sums, counts, logits, chunk_ind):
+    """One chunk's vote, in place (test_mvpnet_3d.py:164-168): sums[chunk_ind[j], c] += logits[c, j] and
+    counts[chunk_ind[j]] += 1 for j < len(chunk_ind). logits [C, ld] f32 as the network returns them, ld >= len(chunk_ind):
+    a padded chunk's extra columns do not vote. chunk_ind int64, distinct. sums [N,C] f32, counts [N] int32."""
+    _dev(sums, counts, logits, chunk_ind)
+    _vote_state(sums, counts)
+    if logits.dim() != 2 or logits.shape[0] != sums.shape[1]:
+        raise RuntimeError("chunk_vote_add: logits [C, ld] with C = %d expected" % sums.shape[1])
+    logits = _f32c(logits)
+    ind = chunk_ind.reshape(-1)
+    if ind.dtype != torch.int64:
+        raise RuntimeError("chunk_vote_add: chunk_ind must be int64")
+    ind = ind.contiguous()
+    if ind.shape[0] > logits.shape[1]:
+        raise RuntimeError("chunk_vote_add: %d indices for %d logit columns" % (ind.shape[0], logits.shape[1]))
+    check(lib().mvk_chunk_vote_add(_p(logits), logits.shape[0], logits.shape[1], _p(ind), ind.shape[0], _p(sums), _p(counts),
+                                   sums.shape[0], _stream()))
+    return sums, counts
+
+
+def _labels64(labels, N, what):
+    labels = labels.reshape(-1)
+    if labels.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8) or labels.shape[0] != N:
+        raise RuntimeError("%s: %d integer labels expected" % (what, N))
+    return labels.to(torch.int64).contiguous()
+
+
+def _confusion_arg(confusion, Cn, device, what):
+    if confusion is None:
+        return torch.zeros((Cn, Cn), device=device, dtype=torch.int64)
+    if confusion.dtype != torch.int64 or tuple(confusion.shape) != (Cn, Cn) or not confusion.is_contiguous():
+        raise RuntimeError("%s: confusion must be a contiguous int64 [C,C] tensor" % what)
+    return confusion
+
+
+def chunk_vote_finish(sums, counts, labels=None, confusion=None, in_place=False):
+    """End of a scene (test_mvpnet_3d.py:171-178): (pred [N] int64, mean [N,C] f32[, confusion [C,C] int64]). mean =
+    sums / max(counts, 1) in float32 (written over sums with in_place), pred = first maximum, C where counts == 0. With
+    labels [N] (integers) the pairs (truth, pred) with both in 0..C-1 are added to `confusion` (created when None), as
+    sklearn's confusion_matrix(labels=arange(C)) counts them."""
+    _dev(sums, counts, labels, confusion)
+    _vote_state(sums, counts)
+    N, Cn = sums.shape
+    mean = sums if in_place else torch.empty_like(sums)
+    pred = torch.empty((N,), device=sums.device, dtype=torch.int64)
+    if labels is not None:
+        labels = _labels64(labels, N, "chunk_vote_finish")
+        confusion = _confusion_arg(confusion, Cn, sums.device, "chunk_vote_finish")
+    elif confusion is not None:
+        raise RuntimeError("chunk_vote_finish: a confusion needs labels")
+    check(lib().mvk_chunk_vote_finish(_p(sums), _p(counts), N, Cn, _p(mean), _p(pred), _p(labels), _p(confusion), _stream()))
+    return (pred, mean) if labels is None else (pred, mean, confusion)
+
+
+def chunk_confusion(pred, labels, num_classes, confusion=None):
+    """confusion [C,C] int64 (HBM) += the pairs (labels[i], pred[i]) with both in 0..C-1; rows = truth."""
+    _dev(pred, labels, confusion)
+    pred = _labels64(pred, pred.numel(), "chunk_confusion")
+    labels = _labels64(labels, pred.shape[0], "chunk_confusion")
+    confusion = _confusion_arg(confusion, int(num_classes), pred.device, "chunk_confusion")
+    check(lib().mvk_chunk_confusion(_p(pred), _p(labels), pred.shape[0], int(num_classes), _p(confusion), _stream()))
+    return confusion

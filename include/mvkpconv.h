@@ -21,6 +21,9 @@
  *   mvk_unproject_depth       KPConv-PyTorch/datasets/ScanNet_sphere_color.py:66-72,409-417
  *   mvk_vote_*                KPConv-PyTorch/utils/tester.py:160-186,223-236,273-297 and utils/trainer.py:351-378,
  *                             :395-412,:497-506 (the NumPy voting loops of test and validation)
+ *   mvk_box_*, mvk_chunk_*    mvpnet/utils/chunk_util.py:4-53, mvpnet/test_mvpnet_3d.py:141-178,
+ *                             mvpnet/evaluate_3d.py:19-36 (the MVPNet baseline's whole-scene test; added under ABI 9,
+ *                             nothing older changed)
  */
 #ifndef MVKPCONV_H
 #define MVKPCONV_H
@@ -714,6 +717,45 @@ int mvk_interpolate_bwd(const float* grad_out, const int64_t* index, const float
                         int64_t N2, float* grad_in, int32_t* status, void* stream);
 int mvk_interpolate_bwd_f64(const double* grad_out, const int64_t* index, const double* weight, int B, int C, int64_t N1,
                             int64_t N2, double* grad_in, int32_t* status, void* stream);
+
+/* ---------------- MVPNet whole-scene test: chunks, logit votes, confusion (csrc/chunk.hip) ------------------------- */
+
+/* Points inside xy boxes (chunk_util.py:39,43). pts [N,3] f32; boxes [n,4] f64 (x_lo, y_lo, x_hi, y_hi), DEVICE. A
+ * point is inside when (double)x >= x_lo && (double)x <= x_hi and the same for y: both ends inclusive, compared in
+ * float64 (exact for float32 coordinates; a NaN coordinate or bound is outside). counts [n] int64 is overwritten with
+ * the members of every box, one launch for all boxes. */
+int mvk_box_count(const float* pts, int64_t N, const double* boxes, int n, int64_t* counts, void* stream);
+/* The members of every box as one CSR, ascending inside a box (np.nonzero order): idx [total] int64 with box b at
+ * offsets[b] .. offsets[b+1] (offsets [n+1] int64, DEVICE, the running sum of the boxes' counts as mvk_box_count gave
+ * them; total = offsets[n]). zmin / zmax [n] f32 (both or neither): minimum and maximum z of each box's members
+ * (+inf / -inf for an empty box). Offsets that are not those of the boxes write nothing outside a box's row or the
+ * buffer. workspace: mvk_box_select_workspace(N, n) bytes, contents need no initialisation.
+ * Neither entry point reads anything back. A caller that cuts a scene into chunks (scene2chunks_legacy) reads, per
+ * scene: the scene's float32 minimum and maximum (six floats, before the boxes exist), the 2 n counts of the inner and
+ * the widened boxes, and -- only when it wants bounding boxes -- zmin / zmax of the kept boxes, which exist only after
+ * the selection that the counts size. Three small reads, none sized by N. */
+int64_t mvk_box_select_workspace(int64_t N, int n);
+int mvk_box_select(const float* pts, int64_t N, const double* boxes, int n, const int64_t* offsets, int64_t total,
+                   int64_t* idx, float* zmin, float* zmax, void* workspace, int64_t workspace_bytes, void* stream);
+/* One chunk's vote (test_mvpnet_3d.py:164-168). logits [C, ld] f32, channel-major as the network returns them, ld >= n:
+ * only the first n columns vote (a padded chunk has more columns than points). chunk_ind [n] int64, DISTINCT (they are
+ * np.nonzero's). sums [N,C] f32 row-major: sums[chunk_ind[j], c] += logits[c, j]; counts [N] int32:
+ * counts[chunk_ind[j]] += 1. Plain read-add-write in stream order, so after the same chunks in the same order the sums
+ * are the reference's float32 sums bit for bit. An index outside [0, N) writes nothing. C <= 64.
+ * Differences from the reference: the visit counter is int32 (the reference's uint8 would wrap at 256 visits, which is
+ * unreachable: a point lies in at most ceil((size + 2 margin) / stride)^2 chunks, 16 at the defaults); what NaN
+ * logits give is not pinned. */
+int mvk_chunk_vote_add(const float* logits, int C, int64_t ld, const int64_t* chunk_ind, int64_t n, float* sums,
+                       int32_t* counts, int64_t N, void* stream);
+/* End of a scene (test_mvpnet_3d.py:171-178, evaluate_3d.py:19-36). mean [N,C] f32 = sums / max(counts, 1), a
+ * correctly rounded float32 division (mean may be sums). pred [N] int64: the first maximum of the mean row, C where
+ * counts == 0. labels [N] int64 and confusion [C,C] int64 (both or neither): confusion[truth, pred] += 1, rows =
+ * truth; a pair whose truth or prediction is outside 0..C-1 is dropped, as confusion_matrix(labels=arange(C)) drops
+ * it (that covers the reference's -100 -> C rewrite and the no-prediction label C). Integer atomics only. */
+int mvk_chunk_vote_finish(const float* sums, const int32_t* counts, int64_t N, int C, float* mean, int64_t* pred,
+                          const int64_t* labels, int64_t* confusion, void* stream);
+/* The confusion alone, for predictions that already exist (Evaluator.update on device tensors). */
+int mvk_chunk_confusion(const int64_t* pred, const int64_t* labels, int64_t N, int C, int64_t* confusion, void* stream);
 
 #ifdef __cplusplus
 }
