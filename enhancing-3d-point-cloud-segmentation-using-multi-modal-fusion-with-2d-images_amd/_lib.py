@@ -164,6 +164,12 @@ _SIGNATURES = {
     "mvk_interpolate_fwd_f64": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _vp]),
     "mvk_interpolate_bwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _vp]),
     "mvk_interpolate_bwd_f64": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _vp]),
+    "mvk_index_csr_workspace": (C.c_int64, [_i, _i64, _i64]),
+    "mvk_index_csr": (C.c_int, [_vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "mvk_interpolate_bwd_csr": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i64, _i64, _vp, _vp]),
+    "mvk_interpolate_bwd_csr_f64": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i64, _i64, _vp, _vp]),
+    "mvk_group_points_bwd_csr": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _i, _vp, _vp]),
+    "mvk_group_points_bwd_csr_f64": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _i, _vp, _vp]),
     "mvk_box_count": (C.c_int, [_vp, _i64, _vp, _i, _vp, _vp]),
     "mvk_box_select_workspace": (C.c_int64, [_i64, _i]),
     "mvk_box_select": (C.c_int, [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),

@@ -32,6 +32,7 @@ SOURCES = [
     ("vote.hip", ["-ffp-contract=off"]),      # float64 vote update in two roundings, like NumPy
     ("pn2.hip", ["-ffp-contract=off"]),       # squared distances in three rounded products and two rounded sums
     ("chunk.hip", ["-ffp-contract=off"]),     # float64 box tests, float32 vote sums and division as NumPy evaluates them
+    ("pn2_ordered.hip", ["-ffp-contract=off"]),   # ordered backwards: a product and its addition are two roundings
 ]
 
 

@@ -21,7 +21,8 @@
 //   ball_query_k   one wave per query, 64 consecutive keys per round: ballot, prefix popcount, ordered write; stops once
 //                  K hits are found. No barrier (a wave leaves early on its own).
 //   knn3_k         one lane per query, key tiles staged in LDS, three sorted slots updated by strict-< insertion.
-//   interp_*_k     one lane per (b, c, n); the backward is a scatter-add with float atomics (not deterministic in order).
+//   interp_*_k     one lane per (b, c, n); the backward is a scatter-add with float atomics (not deterministic in order;
+//                  its fixed-order form is mvk_interpolate_bwd_csr in pn2_ordered.hip).
 #include <limits>
 
 #include "common.h"

@@ -2134,6 +2134,71 @@ def knn_pixels(sphere_points, image_xyz, image_mask, k=3):
     return out
 
 
+# --------------------------------------------------------------------------------------------
+# transposed index of the PointNet++ ops (csrc/pn2_ordered.hip): deterministic mode's gather-form backwards
+# --------------------------------------------------------------------------------------------
+
+def index_csr(index, n1, status=None):
+    """The transposed index of group_points / feature_interpolate (mvk_index_csr): index (B,N2,K) or (B,L) int64 in HBM
+    with keys in [0, n1) -> (row_start, entries), both int32: row (b, j) = entries[row_start[b*n1 + j] :
+    row_start[b*n1 + j + 1]] = the flat positions p = n*K + k of batch element b that hold key j, ascending. Entries
+    outside [0, n1) are in no row; `status` (int32 word in HBM, e.g. pn2_index_status(device)) is set to 1 when one is
+    met. No synchronisation, nothing read back; the scratch is this call's own, so the call can be captured in a graph
+    and two builds may run on two streams."""
+    _dev(index, status)
+    if index.dtype != torch.int64 or index.dim() not in (2, 3):
+        raise RuntimeError("index_csr: expected an int64 index (B,N2,K) or (B,L)")
+    index = index.contiguous()
+    B, n1 = index.shape[0], int(n1)
+    L = index.numel() // B if B > 0 else 0
+    if n1 < 0 or B * L >= 1 << 31 or B * n1 >= 1 << 31:
+        raise RuntimeError("index_csr: B*L = %d and B*n1 = %d must be below 2^31" % (B * L, B * n1))
+    row_start = torch.empty((B * n1 + 1,), device=index.device, dtype=torch.int32)
+    entries = torch.empty((B * L,), device=index.device, dtype=torch.int32)
+    nbytes = lib().mvk_index_csr_workspace(B, L, n1)
+    ws = torch.empty((max(nbytes, 4),), device=index.device, dtype=torch.uint8)
+    check(lib().mvk_index_csr(_p(index), B, L, n1, _p(row_start), _p(entries), _p(status), _p(ws), ws.numel(), _stream()))
+    return row_start, entries
+
+
+_INDEX_CSRS = collections.OrderedDict()
+_INDEX_CSRS_KEPT = 64
+
+
+def _csr_key(index, n1):
+    return (index.device.index, index.data_ptr(), tuple(index.shape), int(n1))
+
+
+def remember_index_csr(index, n1, csr):
+    """Registers csr = index_csr(index, n1) under the index tensor itself, like remember_reverse: the entry holds a weak
+    reference to THAT tensor object and its version counter, so neither another tensor at a recycled address nor the same
+    tensor after an in-place write ever matches."""
+    for k in [k for k, e in _INDEX_CSRS.items() if e[0]() is None]:
+        del _INDEX_CSRS[k]
+    key = _csr_key(index, n1)
+    _INDEX_CSRS[key] = (weakref.ref(index), index._version, csr)
+    _INDEX_CSRS.move_to_end(key)
+    while len(_INDEX_CSRS) > _INDEX_CSRS_KEPT:
+        _INDEX_CSRS.popitem(last=False)
+
+
+def index_csr_for(index, n1):
+    """The (row_start, entries) registered for this very tensor object and key count, or None."""
+    if not (torch.is_tensor(index) and index.is_cuda):
+        return None
+    e = _INDEX_CSRS.get(_csr_key(index, n1))
+    return e[2] if (e is not None and e[0]() is index and e[1] == index._version) else None
+
+
+def _index_csr_shared(owner, index, n1):
+    """The CSR of `index` (the contiguous form of the caller's tensor `owner`), built once per owner."""
+    csr = index_csr_for(owner, n1)
+    if csr is None:
+        csr = index_csr(index, n1)
+        remember_index_csr(owner, n1, csr)
+    return csr
+
+
 class _GroupPointsFn(torch.autograd.Function):
     """mvpnet/ops/group_points.py:5-17; float32 and float64 like the reference's extension."""
 
@@ -2145,6 +2210,7 @@ class _GroupPointsFn(torch.autograd.Function):
         if points.dim() != 3 or index.dim() != 3 or points.shape[0] != index.shape[0]:
             raise RuntimeError("group_points: expected points (B,C,N1) and index (B,N2,K)")
         f64 = points.dtype == torch.float64
+        caller_index = index
         points, index = (points.contiguous() if f64 else _f32c(points)), index.contiguous()
         B, Cc, N1 = points.shape
         _, N2, K = index.shape
@@ -2153,6 +2219,9 @@ class _GroupPointsFn(torch.autograd.Function):
         check(fn(_p(points), _p(index), B, Cc, N1, N2, K, _p(out), _stream()))
         ctx.save_for_backward(index)
         ctx.n1, ctx.f64 = N1, f64
+        # deterministic mode: the backward is a gather over the transposed index, kept under the CALLER's tensor object
+        # (QueryGrouper groups coordinates and features with one index: one CSR)
+        ctx.det, ctx.csr_owner = is_deterministic(), caller_index
         return out
 
     @staticmethod
@@ -2160,6 +2229,12 @@ class _GroupPointsFn(torch.autograd.Function):
         (index,) = ctx.saved_tensors
         g = grad_out.double().contiguous() if ctx.f64 else _f32c(grad_out)
         B, Cc, N2, K = g.shape
+        if ctx.det:
+            row_start, entries = _index_csr_shared(ctx.csr_owner, index, ctx.n1)
+            gi = torch.empty((B, Cc, ctx.n1), device=g.device, dtype=g.dtype)       # every element is written
+            fn = lib().mvk_group_points_bwd_csr_f64 if ctx.f64 else lib().mvk_group_points_bwd_csr
+            check(fn(_p(g), _p(row_start), _p(entries), B, Cc, ctx.n1, N2, K, _p(gi), _stream()))
+            return gi, None
         gi = torch.zeros((B, Cc, ctx.n1), device=g.device, dtype=g.dtype)
         fn = lib().mvk_group_points_bwd_f64 if ctx.f64 else lib().mvk_group_points_bwd
         check(fn(_p(g), _p(index), B, Cc, ctx.n1, N2, K, _p(gi), _stream()))
@@ -2263,7 +2338,10 @@ def set_pn2_index_check(flag):
 
 
 class _FeatureInterpolateFn(torch.autograd.Function):
-    """mvpnet/ops/interpolate.py:5-20. The backward is a float-atomic scatter-add: outside set_deterministic."""
+    """mvpnet/ops/interpolate.py:5-20. The backward is a float-atomic scatter-add by default; when set_deterministic was
+    on in the forward it is the ordered gather over the transposed index (mvk_interpolate_bwd_csr). That CSR is built in
+    the backward every time and not looked up: the build is what reports an index outside the key set, and the 3-NN
+    index of a FeaturePropagation is a new tensor on every forward anyway."""
 
     @staticmethod
     def forward(ctx, feature, index, weight):
@@ -2284,6 +2362,7 @@ class _FeatureInterpolateFn(torch.autograd.Function):
             pn2_check_indices(f.device)
         ctx.save_for_backward(index, w)
         ctx.n1, ctx.f64 = N1, f64
+        ctx.det = is_deterministic()
         return out
 
     @staticmethod
@@ -2291,6 +2370,12 @@ class _FeatureInterpolateFn(torch.autograd.Function):
         index, w = ctx.saved_tensors
         g = grad_out.to(w.dtype).contiguous()
         B, Cc, N2 = g.shape
+        if ctx.det:
+            row_start, entries = index_csr(index, ctx.n1, pn2_index_status(g.device))
+            gi = torch.empty((B, Cc, ctx.n1), device=g.device, dtype=g.dtype)       # every element is written
+            fn = lib().mvk_interpolate_bwd_csr_f64 if ctx.f64 else lib().mvk_interpolate_bwd_csr
+            check(fn(_p(g), _p(w), _p(row_start), _p(entries), B, Cc, ctx.n1, N2, _p(gi), _stream()))
+            return gi, None, None
         gi = torch.zeros((B, Cc, ctx.n1), device=g.device, dtype=g.dtype)
         fn = lib().mvk_interpolate_bwd_f64 if ctx.f64 else lib().mvk_interpolate_bwd
         check(fn(_p(g), _p(index), _p(w), B, Cc, ctx.n1, N2, _p(gi), _p(pn2_index_status(g.device)), _stream()))

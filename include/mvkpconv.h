@@ -708,7 +708,7 @@ int mvk_knn_distance_f64(const double* query, const double* key, int B, int64_t 
 /* Feature interpolation (interpolate_kernel.cu:25-68, :131-174): feature [B,C,N1], index [B,N2,3], weight [B,N2,3] ->
  * out[b,c,n] = sum_k feature[b,c,index[b,n,k]] * weight[b,n,k], accumulated k = 0, 1, 2. Backward: grad_in [B,C,N1]
  * (zero-initialised by the caller) += scatter of grad_out [B,C,N2] * weight, with float atomics (the order of the sum
- * is not fixed). An index outside [0, N1) contributes nothing and sets *status (int32 on the device, or NULL) to 1. */
+ * is not fixed; mvk_interpolate_bwd_csr below is the fixed-order form). An index outside [0, N1) contributes nothing and sets *status (int32 on the device, or NULL) to 1. */
 int mvk_interpolate_fwd(const float* feature, const int64_t* index, const float* weight, int B, int C, int64_t N1,
                         int64_t N2, float* out, int32_t* status, void* stream);
 int mvk_interpolate_fwd_f64(const double* feature, const int64_t* index, const double* weight, int B, int C, int64_t N1,
@@ -717,6 +717,39 @@ int mvk_interpolate_bwd(const float* grad_out, const int64_t* index, const float
                         int64_t N2, float* grad_in, int32_t* status, void* stream);
 int mvk_interpolate_bwd_f64(const double* grad_out, const int64_t* index, const double* weight, int B, int C, int64_t N1,
                             int64_t N2, double* grad_in, int32_t* status, void* stream);
+
+/* ---------------- PointNet++ backwards in a fixed order (csrc/pn2_ordered.hip) ------------------------- */
+/* feature_interpolate and group_points select keys in [0, N1) through an int64 index [B,N2,K] (K = 3 for the
+ * interpolation): per batch element a flat list of L = N2*K positions p = n*K + k. Their backwards below are gathers
+ * over the transposed index: sums in ascending position, no float atomics, every output element written. The atomic
+ * forms above are unchanged and remain the default.
+ *
+ * mvk_index_csr: the transposed index. index [B,L] int64. row_start [B*N1 + 1] int32: the exclusive prefix of the row
+ * lengths, row (b, j) at b*N1 + j, so row_start[B*N1] = the number of entries inside [0, N1). entries [B*L] int32: row
+ * (b, j) = the positions p of batch element b with index[b, p] == j, ASCENDING; only the first row_start[B*N1] words are
+ * defined. An entry outside [0, N1) (the -1 of a ball query without a hit) is in no row; *status (int32 on the device,
+ * or NULL) is set to 1 when one is met. B*L and B*N1 must be below 2^31. workspace: mvk_index_csr_workspace bytes owned
+ * by the caller for the duration of the launches; the call zeroes what it needs zeroed, so the contents need no
+ * initialisation and two builds on two streams need two workspaces. Seven launches with grids fixed by (B, L, N1),
+ * no host synchronisation, nothing read back: capturable. */
+int64_t mvk_index_csr_workspace(int B, int64_t L, int64_t N1);
+int mvk_index_csr(const int64_t* index, int B, int64_t L, int64_t N1, int32_t* row_start, int32_t* entries,
+                  int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+/* grad_in [B,C,N1], every element written (a key without entries gets +0; no zero fill by the caller):
+ *   acc = 0; for p in row (b, j), ascending:  acc = fl(acc + fl(grad_out[b,c,p/3] * weight[b,p]))      interpolation
+ *                                             acc = fl(acc + grad_out[b,c,p])                          grouping
+ * with grad_out [B,C,N2] and weight [B,N2,3] (interpolation) or grad_out [B,C,N2,K] read as [B,C,L] (grouping); every
+ * product and every addition is rounded in the input dtype (no FMA). row_start / entries: mvk_index_csr of the index the
+ * forward used, with the same B, N1 and L = N2*3 (N2*K); an entry outside [0, L) is skipped, nothing is read outside
+ * the first B*L words of entries. A row is summed by one lane: the time grows with the longest row. */
+int mvk_interpolate_bwd_csr(const float* grad_out, const float* weight, const int32_t* row_start, const int32_t* entries,
+                            int B, int C, int64_t N1, int64_t N2, float* grad_in, void* stream);
+int mvk_interpolate_bwd_csr_f64(const double* grad_out, const double* weight, const int32_t* row_start,
+                                const int32_t* entries, int B, int C, int64_t N1, int64_t N2, double* grad_in, void* stream);
+int mvk_group_points_bwd_csr(const float* grad_out, const int32_t* row_start, const int32_t* entries, int B, int C,
+                             int64_t N1, int64_t N2, int K, float* grad_in, void* stream);
+int mvk_group_points_bwd_csr_f64(const double* grad_out, const int32_t* row_start, const int32_t* entries, int B, int C,
+                                 int64_t N1, int64_t N2, int K, double* grad_in, void* stream);
 
 /* ---------------- MVPNet whole-scene test: chunks, logit votes, confusion (csrc/chunk.hip) ------------------------- */
 
