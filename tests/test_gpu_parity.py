@@ -1622,6 +1622,24 @@ def test_fused_clip_sgd_trainer_contract():
 
 # ------------------------------------------------------------------ deformable: regulariser kernel
 
+def regulariser_float64(min_d2, dkp, n, ext, rep, power):
+    """The cited lines of p2p_fitting_regularizer (models/architectures.py:20-58) for ONE layer with tensor ops in float64
+    over the first n rows: (loss term, min_d2[:n] leaf, deformed_KP[:n] leaf) -- differentiate the first wrt the others."""
+    K = min_d2.shape[1]
+    m64 = min_d2.detach().double()[:n].requires_grad_(True)
+    k64 = dkp.detach().double()[:n].requires_grad_(True)
+    l1 = torch.nn.L1Loss()
+    fit = l1(m64 / ext ** 2, torch.zeros_like(m64))
+    locs = k64 / ext
+    rl = 0
+    for i in range(K):
+        other = torch.cat([locs[:, :i, :], locs[:, i + 1:, :]], dim=1).detach()
+        d = torch.sqrt(torch.sum((other - locs[:, i:i + 1, :]) ** 2, dim=2))
+        r = torch.sum(torch.clamp_max(d - rep, max=0.0) ** 2, dim=1)
+        rl = rl + l1(r, torch.zeros_like(r)) / K
+    return power * (2 * fit + rl), m64, k64
+
+
 @pytest.mark.parametrize("N,n", [(300, 300), (2000, 1873), (1, 1)])
 def test_deform_regularizer_kernel_vs_reference_formula(ops, N, n):
     """mvk_deform_regularizer against the cited lines of p2p_fitting_regularizer (models/architectures.py:20-58)
@@ -1634,18 +1652,7 @@ def test_deform_regularizer_kernel_vs_reference_formula(ops, N, n):
     nv = torch.tensor([n], dtype=torch.int32, device="cuda")
     loss = ops.deform_regularizer(min_d2, dkp, ext, rep, power, nv)
     g1, g2 = torch.autograd.grad(loss, [min_d2, dkp])
-    m64 = min_d2.detach().double()[:n].requires_grad_(True)
-    k64 = dkp.detach().double()[:n].requires_grad_(True)
-    l1 = torch.nn.L1Loss()
-    fit = l1(m64 / ext ** 2, torch.zeros_like(m64))
-    locs = k64 / ext
-    rl = 0
-    for i in range(K):
-        other = torch.cat([locs[:, :i, :], locs[:, i + 1:, :]], dim=1).detach()
-        d = torch.sqrt(torch.sum((other - locs[:, i:i + 1, :]) ** 2, dim=2))
-        r = torch.sum(torch.clamp_max(d - rep, max=0.0) ** 2, dim=1)
-        rl = rl + l1(r, torch.zeros_like(r)) / K
-    want = power * (2 * fit + rl)
+    want, m64, k64 = regulariser_float64(min_d2, dkp, n, ext, rep, power)
     w1, w2 = torch.autograd.grad(want, [m64, k64])
     assert abs(loss.item() - want.item()) < 1e-5 * abs(want.item())
     assert rel_err(g1[:n].cpu().numpy(), w1.cpu().numpy()) < 1e-5 and rel_err(g2[:n].cpu().numpy(), w2.cpu().numpy()) < 1e-5
