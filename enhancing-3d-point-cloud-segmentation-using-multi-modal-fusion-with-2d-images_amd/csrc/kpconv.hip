@@ -10,10 +10,10 @@
 // w[n,h,k] is a pure function of geometry (q, s, kernel points, extent), so the
 // backward recomputes it instead of storing [N,H,K].
 //
-// Work decomposition (one 64-lane wavefront per workgroup): see the comment on
-// kpconv_gather_vec (forward, rigid) and kpconv_lane_channel (backward scatter dx, deformable forward:
-// lane = channel, one point per wave, wave-uniform neighbour loop). The offset gradient of the deformable
-// layers is csrc/deform.hip (lane = neighbour).
+// Work decomposition: see the comment on kpconv_gather_mfma (forward with linear influence and sum aggregation,
+// rigid and deformable: one point per wave on the matrix pipe) and kpconv_lane_channel (backward scatter dx, and the
+// forward of every other layer: lane = channel, one point per wave, wave-uniform neighbour loop). The offset
+// gradient of the deformable layers is csrc/deform.hip (lane = neighbour).
 #include <type_traits>
 
 #include "common.h"
@@ -39,9 +39,10 @@ struct KPParams {
   int H, Cin, K;
   float extent;
   int influence, aggregation;
-  const int32_t* order;  // vector gather (rigid): work list -- the wave working on slots w .. w+PPW-1 takes the points order[w ..] (a
+  const int32_t* order;  // MFMA gather (its only reader): work list -- the wave working on slot w takes the point order[w] (a
                          // spatially sorted permutation of 0 .. Nq-1); results land in the points' own rows. null: slot = point
-  int xcd_blocks;        // with `order`: the first xcd_blocks workgroups are dealt to the 8 XCDs as 8 contiguous runs of the work list
+  int xcd_blocks;        // MFMA gather, with `order`: the first xcd_blocks workgroups are dealt to the 8 XCDs as 8 contiguous
+                         // runs of the work list
   // MFMA gather, KPM = 2 (gather-form feature gradient of a deformable layer): the kernel points belong to the NEIGHBOUR
   // rows -- nb_offsets [rows of s, K, 3] are added to kp (and the sum is used negated: the relation is transposed) -- and
   // every weight is multiplied by nb_mod [rows of s, K] (modulated layers; null: 1)
@@ -66,23 +67,21 @@ __device__ __forceinline__ void wave_sync_lds() {   // LDS hand-off inside ONE w
 }
 
 // ---------------------------------------------------------------------------
-// Phase A (shared): fills rel[64] (xyz + neighbour row or -1) and w[64][16]. One WAVE works on its own rel / wl
-// (the hand-offs are wave-level: a workgroup may hold several independent waves).
-// Lane mapping: A1 lane = ph = p*HC + h ; A2 item = t*64 + lane, k = lane & 15, ph = item >> 4.
-// WPAD = extra floats between consecutive points' weight blocks (bank spreading).
-// Returns the lane's neighbour row j (A1 mapping) so callers can shuffle it.
+// Phase A of the lane = channel kernel: for the 64 columns h0 .. h0 + 63 of point n's row, fills rel[64] (xyz +
+// neighbour row or -1) and w[64][16]. One WAVE works on its own rel / wl (the hand-offs are wave-level: a workgroup may
+// hold several independent waves).
+// Lane mapping: A1 lane = column h ; A2 item = t*64 + lane, k = lane & 15, column = item >> 4.
+// Returns the lane's neighbour row j (A1 mapping).
 // ---------------------------------------------------------------------------
-template <int PPW, int HC, int WPAD, bool IDX64, bool DEFORM>
-__device__ __forceinline__ int phase_a(const KPParams& P, int64_t n0, int h0, int lane,
+template <bool IDX64, bool DEFORM>
+__device__ __forceinline__ int phase_a(const KPParams& P, int64_t n, int h0, int lane,
                                        float4* rel, float* wl, float qx, float qy, float qz,
-                                       bool nvalid, float kx, float ky, float kz,
-                                       float* run_min /* DEFORM only, PPW==1 */, int* run_arg = nullptr) {
-  const int p = lane / HC, h = lane % HC;
-  const int64_t n = n0 + p;
+                                       float kx, float ky, float kz,
+                                       float* run_min /* DEFORM only */, int* run_arg = nullptr) {
   int j = -2;  // -2: no entry, -1: shadow entry
   float rx = 0.f, ry = 0.f, rz = 0.f;
-  if (nvalid && h0 + h < P.H) {
-    j = load_idx<IDX64>(P.idx, n * P.H + h0 + h, P.Ns);
+  if (h0 + lane < P.H) {
+    j = load_idx<IDX64>(P.idx, n * P.H + h0 + lane, P.Ns);
     if (j >= 0) {
       const float* sp = P.s + (int64_t)j * 3;
       rx = sp[0] - qx;
@@ -144,7 +143,7 @@ __device__ __forceinline__ int phase_a(const KPParams& P, int64_t n0, int h0, in
         if (run_arg) *run_arg = h0 + ph;
       }
     }
-    wl[(ph / HC) * (HC * 16 + WPAD) + (ph % HC) * 16 + k] = w;
+    wl[ph * 16 + k] = w;
   }
   wave_sync_lds();
   return j;
@@ -160,12 +159,12 @@ __device__ __forceinline__ int phase_a(const KPParams& P, int64_t n0, int h0, in
 // row. No LDS, no phase A / phase B hand-off, no per-neighbour loop of 15 x 4 FMAs per lane: per group of four
 // neighbours a wave issues 5 cross-lane reads (the neighbour's row and relative position, read once per 64 columns by the
 // lane of that column), ~12 VALU instructions for its weight, T dword loads (16 lanes = 64 contiguous bytes of a row) and
-// T MFMAs. The vector kernel below is bound by its own instruction stream (15 x 4 v_pk_fma_f32 per neighbour and lane:
+// T MFMAs. The vector kernel it replaced was bound by its own instruction stream (15 x 4 v_pk_fma_f32 per neighbour and lane:
 // 57 us for 19 464 x 66 against a 28 us floor of pure FMA issue); here the products run on the matrix
 // pipe (exact f32 products, f32 accumulation -- four neighbours per step instead of one: another summation order,
 // ~1e-7), 56 MFMAs of 32 cycles per point of that layer = 14 us chip-wide.
 // One wave per query point (waves of a workgroup are independent), T accumulator tiles of 16 channels (4 VGPRs each);
-// rows wider than 16 T channels run as gridDim.y channel blocks. The work list / XCD runs are those of the vector kernel.
+// rows wider than 16 T channels run as gridDim.y channel blocks. Work list / XCD runs: KPParams::order, xcd_blocks.
 // ---------------------------------------------------------------------------
 typedef float mfma_f32x4 __attribute__((ext_vector_type(4)));
 
@@ -205,7 +204,8 @@ __global__ __launch_bounds__(256) void kpconv_gather_mfma(KPParams P) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int m = lane & 15, kq = lane >> 4;
   int64_t blk = blockIdx.x;
-  if ((int)blockIdx.x < P.xcd_blocks) {      // XCD x works on one contiguous run of the work list (see kpconv_gather_vec)
+  if ((int)blockIdx.x < P.xcd_blocks) {      // workgroups go to the XCDs round robin (b % 8): XCD x then works on
+    // ONE contiguous run of the sorted work list, so that the rows its L2 pulls are those of one region of the cloud
     const int xq = P.xcd_blocks >> 3, xr = P.xcd_blocks & 7, xc = blockIdx.x & 7;
     blk = (int64_t)xc * xq + min(xc, xr) + (blockIdx.x >> 3);
   }
@@ -370,7 +370,7 @@ __global__ __launch_bounds__(256) void kpconv_gather_mfma(KPParams P) {
   }
   if (KPM == 1 && P.min_d2 != nullptr && blockIdx.y == 0) {
     // the four column residues of kernel point m: smaller distance wins, equal distances the smaller column (the FIRST
-    // arg-min over all columns, like the sequential scan of the vector kernel)
+    // arg-min over all columns, like a sequential scan)
 #pragma unroll
     for (int o = 16; o < 64; o <<= 1) {
       const float od = __shfl_xor(run_min, o);
@@ -413,375 +413,8 @@ __global__ __launch_bounds__(256) void kpconv_gather_mfma(KPParams P) {
 }
 
 // ---------------------------------------------------------------------------
-// Vector gather kernel (rigid KPConv, any Cin <= 4*64*NCH).
-//   LPP lanes own one query point (4 channels per lane and channel chunk), PPW = 64/LPP points per
-//   wave, neighbours in chunks of HC = 64/PPW per point. LPP/PPW/HC are launch parameters so that
-//   e.g. Cin = 66 runs with LPP = 17, PPW = 3 (80 % of the lanes busy) instead of a padded power of 2.
-//   Phase A: lane (p,h) gathers its neighbour's xyz and evaluates all K kernel-point correlations
-//            itself (kernel points are wave-uniform -> scalar registers), then writes one 64-byte LDS
-//            row {w[0..14], neighbour row index}.
-//   Phase B: per neighbour, the point group reads that row (4 x ds_read_b128, broadcast inside the
-//            group, rows of different groups are skewed by 16 B to spread banks), loads the
-//            16-byte slice of the feature row and does K x 4 FMAs (v_pk_fma_f32).
-//   FAST = linear influence + sum aggregation (the network default): sqrt via v_sqrt_f32 and a
-//   multiplication by 1/extent (1 ulp class differences, far inside the 1e-4 parity bar).
-// ---------------------------------------------------------------------------
-// GWPB independent waves per workgroup (nothing is shared between them): one-wave workgroups are
-// dispatched too slowly to keep the SIMDs' wave slots filled (measured 2.3 resident waves per SIMD of 4)
-constexpr int GWPB = 4;
-
-
-// 4 consecutive channels of a feature row / of the aggregate
-typedef float f4v __attribute__((ext_vector_type(4)));        // accumulator quad
-__device__ __forceinline__ float4 as_float4(f4v v) { return make_float4(v.x, v.y, v.z, v.w); }
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
-// DEFORM (deformable layers, blocks.py:286-327; LPP >= 4 so that PPW <= 16): every point's deformed kernel points
-// (kernel point + its offset) live in LDS, phase A reads them instead of the wave-uniform rigid ones, drops the
-// neighbours that no deformed kernel point reaches (their row index becomes the shadow -> phase B skips them) and
-// writes a second LDS row with the 15 squared distances, from which the lanes (point, kernel point, column
-// residue) keep the running (min, first arg-min column) over ALL entries, shadow included (blocks.py:303).
-// The deformable levels are the coarse ones (hundreds of points, hundreds of neighbour columns), so the GWPB
-// waves of a workgroup share the SAME points and take every GWPB-th neighbour chunk; wave 0 adds the partial
-// aggregates (LDS, fixed order -> deterministic) and writes A / min_d2 / min_arg.
-constexpr int DPPW = 16;      // most points per wave of the deformable variant
-
-template <int NCH, bool IDX64, bool FAST, bool DEFORM = false>
-__global__ __launch_bounds__(64 * GWPB, NCH == 1 ? 4 : 2) void kpconv_gather_vec(KPParams P, int LPP, int PPW, int HC) {
-  // DEFORM: the nwv waves of the workgroup share the same PPW points and take every nwv-th neighbour chunk; wave 0
-  // adds the partial aggregates through LDS in a fixed order and stores them.
-  const int nwv = blockDim.x >> 6;
-  const float* __restrict__ X = P.x;      // features [Ns,Cin]
-  float* __restrict__ Aout = P.A;         // aggregate [Nq,K,Cin]
-  constexpr int UB = NCH == 1 ? 6 : 4;    // feature rows in flight per lane
-  __shared__ __align__(16) float wl_all[GWPB][64 * 16 + 64 * 4];
-  __shared__ float d2_all[DEFORM ? GWPB : 1][DEFORM ? 64 * 16 + DPPW * 16 : 1];  // squared distances of the chunk (rows skewed by point)
-  __shared__ float4 kd[DEFORM ? DPPW * 16 : 1];                                 // deformed kernel points per point
-  const int wid = threadIdx.x >> 6;
-  float* wl = wl_all[wid];
-  float* d2l = d2_all[DEFORM ? wid : 0];
-  const int lane = threadIdx.x & 63;
-  const int32_t* __restrict__ ord = DEFORM ? nullptr : P.order;
-  int64_t blk = blockIdx.x;
-  if (!DEFORM && (int)blockIdx.x < P.xcd_blocks) {
-    // workgroups go to the XCDs round robin (b % 8): XCD x then works on ONE contiguous run of the sorted work list,
-    // so that the rows its L2 pulls are those of one region of the cloud
-    const int xq = P.xcd_blocks >> 3, xr = P.xcd_blocks & 7, xc = blockIdx.x & 7;
-    blk = (int64_t)xc * xq + min(xc, xr) + (blockIdx.x >> 3);
-  }
-  const int64_t n0 = DEFORM ? (int64_t)blockIdx.x * PPW : (blk * GWPB + wid) * PPW;
-  const int hbeg = DEFORM ? wid * HC : 0, hstep = DEFORM ? nwv * HC : HC;        // this wave's neighbour chunks
-  // phase-A identity: (point pa, neighbour slot ha)
-  const int pa = lane / HC, ha = lane - pa * HC;
-  const bool a_on = pa < PPW && n0 + pa < P.Nq;
-  const int64_t na = (a_on && ord) ? (int64_t)ord[n0 + pa] : n0 + pa;      // the point of this lane's phase-A identity
-  float qx = 0.f, qy = 0.f, qz = 0.f;
-  if (a_on) {
-    const float* qp = P.q + na * 3;
-    qx = qp[0];
-    qy = qp[1];
-    qz = qp[2];
-  }
-  float* wrow_a = wl + (pa * HC + ha) * 16 + pa * 4;
-  // phase-B identity: (point pb, channel quad cl)
-  const int pb = lane / LPP, cl = lane - pb * LPP;
-  const int64_t nslot = n0 + pb;
-  const bool b_on = pb < PPW && nslot < P.Nq;
-  const float* wblk_b = wl + pb * (HC * 16 + 4);
-  const float inv_ext = 1.0f / P.extent;
-  const float* __restrict__ kp = P.kp;
-  const float ext2 = P.extent * P.extent;
-  // DEFORM scan identity: pair (point, k) = pk, of which there are NPK = 16 PPW. NPK >= 64: pairs lane + 64 t, every
-  // column. NPK < 64: pair lane % NPK, columns congruent to lane / NPK modulo NSUB = 64 / NPK.
-  const int NPK = PPW * 16;
-  const int NSUB = NPK >= 64 ? 1 : 64 / NPK;
-  const int sub = NPK >= 64 ? 0 : lane / NPK;
-  float run_min[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
-  int run_arg[4] = {0x7fffffff, 0x7fffffff, 0x7fffffff, 0x7fffffff};
-  if (DEFORM) {
-    for (int e = threadIdx.x; e < DPPW * 16; e += blockDim.x) {
-      const int pp = e >> 4, kk = e & 15;
-      float4 v = make_float4(1e9f, 1e9f, 1e9f, 0.f);        // slots beyond K / beyond the last point: out of every range
-      if (kk < P.K && n0 + pp < P.Nq) {
-        const float* o = P.offsets + ((n0 + pp) * P.K + kk) * 3;
-        v = make_float4(kp[kk * 3] + o[0], kp[kk * 3 + 1] + o[1], kp[kk * 3 + 2] + o[2], 0.f);   // blocks.py:287
-      }
-      kd[e] = v;
-    }
-    __syncthreads();
-  }
-
-  f4v acc[NCH][KMAX - 1];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-#pragma unroll
-    for (int kk = 0; kk < KMAX - 1; ++kk) acc[c][kk] = f4v{0.f, 0.f, 0.f, 0.f};
-
-  // software pipeline over neighbour chunks: index two chunks ahead, support xyz one chunk ahead
-  auto ld_j = [&](int h) -> int {
-    return (a_on && h < P.H) ? load_idx<IDX64>(P.idx, na * P.H + h, P.Ns) : -2;
-  };
-  int jA = ld_j(hbeg + ha), jB = ld_j(hbeg + hstep + ha);
-  float sx = 0.f, sy = 0.f, sz = 0.f;
-  if (jA >= 0) {
-    const float* sp = P.s + (int64_t)jA * 3;
-    sx = sp[0];
-    sy = sp[1];
-    sz = sp[2];
-  }
-  for (int h0 = hbeg; h0 < P.H; h0 += hstep) {
-    const int jC = ld_j(h0 + 2 * hstep + ha);
-    float tx = 0.f, ty = 0.f, tz = 0.f;
-    if (jB >= 0) {
-      const float* sp = P.s + (int64_t)jB * 3;
-      tx = sp[0];
-      ty = sp[1];
-      tz = sp[2];
-    }
-    // ---------------- phase A: this lane's neighbour against every kernel point
-    float wv[16];
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) wv[kk] = 0.f;
-    int jrow = jA;                 // row index phase B sees (DEFORM: shadow for neighbours out of every range)
-    if (DEFORM) {
-      // entry present (real or shadow, blocks.py:277): distances to the point's deformed kernel points
-      float dv[16];
-      bool inrange = false;
-      float bd = INFINITY;
-      int bk = 0;
-      const float rx = (jA >= 0 ? sx : 1e6f) - qx, ry = (jA >= 0 ? sy : 1e6f) - qy, rz = (jA >= 0 ? sz : 1e6f) - qz;
-#pragma unroll
-      for (int kk = 0; kk < KMAX - 1; ++kk) {
-        const float4 kq = kd[(pa < PPW ? pa : 0) * 16 + kk];
-        const float dx = rx - kq.x, dy = ry - kq.y, dz = rz - kq.z;
-        const float d2 = dx * dx + dy * dy + dz * dz;  // blocks.py:294-297
-        dv[kk] = jA >= -1 ? d2 : INFINITY;
-        if (jA >= 0) {
-          inrange = inrange || d2 < ext2;
-          wv[kk] = FAST ? fmaxf(1.0f - __builtin_amdgcn_sqrtf(d2) * inv_ext, 0.0f) : influence_w(d2, P.extent, P.influence);
-          if (!FAST && kk < P.K && d2 < bd) {
-            bd = d2;
-            bk = kk;
-          }
-        }
-      }
-      dv[15] = INFINITY;
-      if (!FAST && P.aggregation == MVK_AGG_CLOSEST) {  // one-hot of the first arg-min (blocks.py:349-351)
-#pragma unroll
-        for (int kk = 0; kk < KMAX - 1; ++kk)
-          if (kk != bk) wv[kk] = 0.f;
-      }
-      if (!inrange) {                      // dropped by the in-range filter (blocks.py:306-325)
-#pragma unroll
-        for (int kk = 0; kk < KMAX - 1; ++kk) wv[kk] = 0.f;
-        if (jA >= 0) jrow = -1;
-      }
-      float4* dd = reinterpret_cast<float4*>(d2l + lane * 16 + pa * 16);
-      dd[0] = make_float4(dv[0], dv[1], dv[2], dv[3]);
-      dd[1] = make_float4(dv[4], dv[5], dv[6], dv[7]);
-      dd[2] = make_float4(dv[8], dv[9], dv[10], dv[11]);
-      dd[3] = make_float4(dv[12], dv[13], dv[14], dv[15]);
-    } else if (jA >= 0) {
-      const float rx = sx - qx, ry = sy - qy, rz = sz - qz;
-      float bd = INFINITY;
-      int bk = 0;
-#pragma unroll
-      for (int kk = 0; kk < KMAX - 1; ++kk) {
-        if (kk < P.K) {
-          const float dx = rx - kp[kk * 3], dy = ry - kp[kk * 3 + 1], dz = rz - kp[kk * 3 + 2];
-          const float d2 = dx * dx + dy * dy + dz * dz;  // blocks.py:294-297
-          if (FAST) {
-            wv[kk] = fmaxf(1.0f - __builtin_amdgcn_sqrtf(d2) * inv_ext, 0.0f);  // blocks.py:335-338
-          } else {
-            wv[kk] = influence_w(d2, P.extent, P.influence);
-            if (d2 < bd) {
-              bd = d2;
-              bk = kk;
-            }
-          }
-        }
-      }
-      if (!FAST && P.aggregation == MVK_AGG_CLOSEST) {  // one-hot of the first arg-min (blocks.py:349-351)
-#pragma unroll
-        for (int kk = 0; kk < KMAX - 1; ++kk)
-          if (kk != bk) wv[kk] = 0.f;
-      }
-    }
-    wv[15] = __int_as_float(jrow);
-    {
-      float4* dst = reinterpret_cast<float4*>(wrow_a);
-      dst[0] = make_float4(wv[0], wv[1], wv[2], wv[3]);
-      dst[1] = make_float4(wv[4], wv[5], wv[6], wv[7]);
-      dst[2] = make_float4(wv[8], wv[9], wv[10], wv[11]);
-      dst[3] = make_float4(wv[12], wv[13], wv[14], wv[15]);
-    }
-    wave_sync_lds();
-    if (DEFORM) {      // running (min, first column) of d2 per (point, kernel point)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int e = lane + 64 * t;
-        const int pk = NPK >= 64 ? e : lane - sub * NPK;
-        if (pk < NPK && sub < NSUB && e < (NPK >= 64 ? NPK : 64)) {
-          const int pp = pk >> 4, kk = pk & 15;
-          for (int h = sub; h < HC; h += NSUB) {
-            const float d = d2l[(pp * HC + h) * 16 + pp * 16 + kk];
-            if (d < run_min[t]) {           // strict: this lane visits its columns in ascending order
-              run_min[t] = d;
-              run_arg[t] = h0 + h;
-            }
-          }
-        }
-      }
-    }
-    // ---------------- phase B: UB feature rows in flight, then their FMAs
-    const uint64_t live = __ballot(jrow >= 0);        // bit = phase-A lane (point pa, column ha) holds a real neighbour
-    if (live != 0ull) {
-      for (int hb = 0; hb < HC; hb += UB) {
-        int jj[UB];
-        float4 xv[UB][NCH];
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-          jj[u] = (hb + u < HC && b_on) ? __float_as_int(wblk_b[(hb + u) * 16 + 15]) : -2;
-#pragma unroll
-          for (int c = 0; c < NCH; ++c) {
-            const int c4 = (cl + c * LPP) * 4;
-            xv[u][c] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (jj[u] >= 0 && c4 < P.Cin) {
-              const float* xr = X + (int64_t)jj[u] * P.Cin + c4;
-              if (c4 + 3 < P.Cin) {
-                xv[u][c] = ld4(xr);
-              } else {  // ragged tail of a row whose length is not a multiple of 4
-                xv[u][c].x = (float)xr[0];
-                if (c4 + 1 < P.Cin) xv[u][c].y = (float)xr[1];
-                if (c4 + 2 < P.Cin) xv[u][c].z = (float)xr[2];
-                if (c4 + 3 < P.Cin) xv[u][c].w = (float)xr[3];
-              }
-            }
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-          if (jj[u] >= 0) {
-            const float4* w4 = reinterpret_cast<const float4*>(wblk_b + (hb + u) * 16);
-            const float4 wa = w4[0], wb = w4[1], wc = w4[2], wd = w4[3];
-            const float wk[15] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w,
-                                  wc.x, wc.y, wc.z, wc.w, wd.x, wd.y, wd.z};
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-#pragma unroll
-              for (int kk = 0; kk < KMAX - 1; ++kk) {
-                acc[c][kk].x += wk[kk] * xv[u][c].x;
-                acc[c][kk].y += wk[kk] * xv[u][c].y;
-                acc[c][kk].z += wk[kk] * xv[u][c].z;
-                acc[c][kk].w += wk[kk] * xv[u][c].w;
-              }
-            }
-          }
-        }
-      }
-    }
-    wave_sync_lds();
-    jA = jB;
-    jB = jC;
-    sx = tx;
-    sy = ty;
-    sz = tz;
-  }
-  if (DEFORM) {
-    // partial aggregates of waves 1..nwv-1 -> wave 0, five kernel points per round through the waves' weight rows
-    __syncthreads();
-    float4* mine = reinterpret_cast<float4*>(wl_all[wid]);        // [5][64] float4 = the wave's 1280 floats
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        if (wid > 0) {
-#pragma unroll
-          for (int q5 = 0; q5 < 5; ++q5) mine[q5 * 64 + lane] = as_float4(acc[c][r * 5 + q5]);
-        }
-        __syncthreads();
-        if (wid == 0) {
-          for (int w = 1; w < nwv; ++w) {
-            const float4* theirs = reinterpret_cast<const float4*>(wl_all[w]);
-#pragma unroll
-            for (int q5 = 0; q5 < 5; ++q5) {
-              const float4 v = theirs[q5 * 64 + lane];
-              acc[c][r * 5 + q5].x += v.x;
-              acc[c][r * 5 + q5].y += v.y;
-              acc[c][r * 5 + q5].z += v.z;
-              acc[c][r * 5 + q5].w += v.w;
-            }
-          }
-        }
-        __syncthreads();
-      }
-    }
-  }
-  if (DEFORM) {
-    // (min, column) candidates of every wave and column residue
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      wl[t * 64 + lane] = run_min[t];
-      wl[256 + t * 64 + lane] = __int_as_float(run_arg[t]);
-    }
-    __syncthreads();
-    if (wid == 0 && P.min_d2 != nullptr) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int pk = lane + 64 * t;
-        if (pk < NPK && (NPK >= 64 || t == 0)) {
-          float m = INFINITY;
-          int a = 0x7fffffff;
-          for (int w = 0; w < nwv; ++w)
-            for (int sb = 0; sb < NSUB; ++sb) {
-              const int slot = NPK >= 64 ? pk : sb * NPK + pk;
-              const float om = wl_all[w][slot];
-              const int oa = __float_as_int(wl_all[w][256 + slot]);
-              if (om < m || (om == m && oa < a)) {
-                m = om;
-                a = oa;
-              }
-            }
-          const int pp = pk >> 4, kk = pk & 15;
-          if (kk < P.K && n0 + pp < P.Nq) {
-            P.min_d2[(n0 + pp) * P.K + kk] = m;
-            if (P.min_arg) P.min_arg[(n0 + pp) * P.K + kk] = a == 0x7fffffff ? 0 : a;
-          }
-        }
-      }
-    }
-  }
-  if (b_on && (!DEFORM || wid == 0)) {
-    const int64_t n = ord ? (int64_t)ord[nslot] : nslot;      // the row of this lane's phase-B identity
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int c4 = (cl + c * LPP) * 4;
-      if (c4 < P.Cin) {
-#pragma unroll
-        for (int kk = 0; kk < KMAX - 1; ++kk) {
-          if (kk < P.K) {
-            // (the f32 instantiations keep the dense [Nq,K,Cin] addressing: they sit at their register limit)
-            float* o = Aout + (n * P.K + kk) * P.Cin + c4;
-            if (c4 + 3 < P.Cin) {
-              st4(o, as_float4(acc[c][kk]));
-            } else {
-              o[0] = acc[c][kk].x;
-              if (c4 + 1 < P.Cin) o[1] = acc[c][kk].y;
-              if (c4 + 2 < P.Cin) o[2] = acc[c][kk].z;
-              if (c4 + 3 < P.Cin) o[3] = acc[c][kk].w;
-            }
-          }
-        }
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Generic lane = channel kernel (one point per wave). MODE 0: forward gather
-// (any Cin, rigid or deformable). MODE 1: backward scatter (+ deformable grads).
+// Generic lane = channel kernel (one point per wave). MODE 0: forward of every layer the MFMA gather does not take
+// (any influence, aggregation, Cin and table size, rigid or deformable). MODE 1: backward scatter (+ deformable grads).
 // Channels handled: c = c0 + lane + 64*slot, slot < NSLOT.
 // ---------------------------------------------------------------------------
 // WPB > 1 (backward scatter of the layers searched at the deform radius: hundreds of neighbour columns for a few
@@ -793,7 +426,7 @@ __global__ __launch_bounds__(64 * GWPB, NCH == 1 ? 4 : 2) void kpconv_gather_vec
 // (85 points, 512 channels): 85 waves -> 2 720.
 template <int NSLOT, bool IDX64, int MODE, bool DEFORM, int WPB = 1, int HS = 1>
 __global__ __launch_bounds__(64 * WPB * HS) void kpconv_lane_channel(KPParams P, int c0_base) {
-  constexpr int HC = 64, WPAD = 0;
+  constexpr int HC = 64;
   static_assert(WPB == 1 || MODE == 1, "only the scatter splits a point over waves");
   static_assert(HS == 1 || (MODE == 1 && WPB == 1 && !DEFORM), "neighbour interleave: rigid scatter only");
   const int c0 = c0_base + (int)blockIdx.y * 64 * NSLOT;
@@ -836,8 +469,7 @@ __global__ __launch_bounds__(64 * WPB * HS) void kpconv_lane_channel(KPParams P,
   }
 
   for (int h0 = wid * HC; h0 < P.H; h0 += HC * WPB) {
-    int j = phase_a<1, HC, WPAD, IDX64, DEFORM>(P, n, h0, lane, rel, wl, qx, qy, qz, true, kx, ky,
-                                                 kz, &run_min, &run_arg);
+    int j = phase_a<IDX64, DEFORM>(P, n, h0, lane, rel, wl, qx, qy, qz, kx, ky, kz, &run_min, &run_arg);
     if (__ballot(j >= 0) != 0ull) {
       const int hend = min(HC, P.H - h0);
       for (int hh = HS > 1 ? wid_all : 0; hh < hend; hh += HS) {
@@ -898,144 +530,7 @@ __global__ __launch_bounds__(64 * WPB * HS) void kpconv_lane_channel(KPParams P,
   }
 }
 
-// ---------------------------------------------------------------------------
-// Rigid gather for rows of <= 4 channels (the first layer of the baseline / middle- / late-fusion nets: features
-// (1, z) or (1, r, g, b)). The vector kernel would run with one lane per point AND one neighbour per chunk --
-// an LDS round trip and a barrier per neighbour (119 us for 19 464 points). Here SLP = 4 lanes own a point: lane
-// `sub` takes the neighbours sub, sub + 4, ... in batches of four (indices, then xyz + feature rows, then the
-// products), all accumulators (15 x <= 4) in registers, no LDS; the four partial aggregates are added by two
-// butterfly steps at the end (one lane per point alone leaves 304 waves on 1 024 SIMDs, each a 50 us chain).
-// ---------------------------------------------------------------------------
-template <bool IDX64, bool FAST>
-__global__ __launch_bounds__(256) void kpconv_gather_small(KPParams P) {
-  constexpr int SLP = 4;
-  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int sub = (int)(gid & (SLP - 1));
-  const bool live = gid / SLP < P.Nq;                      // (whole waves take part in the shuffles below)
-  const int64_t n = live ? gid / SLP : P.Nq - 1;
-  const float qx = P.q[n * 3], qy = P.q[n * 3 + 1], qz = P.q[n * 3 + 2];
-  const float inv_ext = 1.0f / P.extent;
-  const float* __restrict__ kp = P.kp;
-  const int Cin = P.Cin;
-  float acc[KMAX - 1][4];
-#pragma unroll
-  for (int kk = 0; kk < KMAX - 1; ++kk)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[kk][c] = 0.f;
-  constexpr int UBS = 4;
-  for (int h0 = sub; h0 < P.H; h0 += UBS * SLP) {
-    int j[UBS];
-#pragma unroll
-    for (int u = 0; u < UBS; ++u)
-      j[u] = h0 + u * SLP < P.H ? load_idx<IDX64>(P.idx, n * P.H + h0 + u * SLP, P.Ns) : -1;
-    float sx[UBS], sy[UBS], sz[UBS], xv[UBS][4];
-#pragma unroll
-    for (int u = 0; u < UBS; ++u) {
-      const int64_t jj = j[u] >= 0 ? j[u] : 0;                  // shadow entries read row 0 and are not applied
-      sx[u] = P.s[jj * 3];
-      sy[u] = P.s[jj * 3 + 1];
-      sz[u] = P.s[jj * 3 + 2];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) xv[u][c] = c < Cin ? P.x[jj * Cin + c] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < UBS; ++u) {
-      if (j[u] < 0) continue;
-      const float rx = sx[u] - qx, ry = sy[u] - qy, rz = sz[u] - qz;
-      float wv[KMAX - 1];
-      float bd = INFINITY;
-      int bk = 0;
-#pragma unroll
-      for (int kk = 0; kk < KMAX - 1; ++kk) {
-        wv[kk] = 0.f;
-        if (kk < P.K) {
-          const float dx = rx - kp[kk * 3], dy = ry - kp[kk * 3 + 1], dz = rz - kp[kk * 3 + 2];
-          const float d2 = dx * dx + dy * dy + dz * dz;  // blocks.py:294-297
-          if (FAST) {
-            wv[kk] = fmaxf(1.0f - __builtin_amdgcn_sqrtf(d2) * inv_ext, 0.0f);  // blocks.py:335-338
-          } else {
-            wv[kk] = influence_w(d2, P.extent, P.influence);
-            if (d2 < bd) {
-              bd = d2;
-              bk = kk;
-            }
-          }
-        }
-      }
-      if (!FAST && P.aggregation == MVK_AGG_CLOSEST) {  // one-hot of the first arg-min (blocks.py:349-351)
-#pragma unroll
-        for (int kk = 0; kk < KMAX - 1; ++kk)
-          if (kk != bk) wv[kk] = 0.f;
-      }
-#pragma unroll
-      for (int kk = 0; kk < KMAX - 1; ++kk)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[kk][c] += wv[kk] * xv[u][c];
-    }
-  }
-#pragma unroll
-  for (int kk = 0; kk < KMAX - 1; ++kk)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      acc[kk][c] += __shfl_xor(acc[kk][c], 1);
-      acc[kk][c] += __shfl_xor(acc[kk][c], 2);
-    }
-  if (!live) return;
-#pragma unroll
-  for (int kk = 0; kk < KMAX - 1; ++kk) {
-    if (kk < P.K && (kk & (SLP - 1)) == sub) {             // the four lanes share the stores
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (c < Cin) P.A[(n * P.K + kk) * Cin + c] = acc[kk][c];
-    }
-  }
-}
-
-// Launch geometry of the vector gather kernel for one layer (also exported: mvk_kpconv_gather_plan).
-struct VecPlan {
-  int LPP, PPW, HC;   // lanes per point, points per wave, neighbours per chunk and point
-  int nw;             // waves per workgroup
-  int64_t wgs;        // workgroups
-};
-
-VecPlan plan_vec(int64_t Nq, int H, int Cin, bool deform) {
-  VecPlan v{};
-  const int c4 = (Cin + 3) / 4;
-  v.LPP = c4 < 64 ? c4 : 64;
-  v.PPW = 64 / v.LPP;
-  v.HC = 64 / v.PPW;
-  const int64_t groups = cdiv64(Nq, v.PPW);               // point groups
-  if (deform) {       // one workgroup per point group, its waves share the group's neighbour chunks (kernel comment)
-    const int chunks = (H + v.HC - 1) / v.HC;
-    v.nw = chunks < GWPB ? (chunks < 1 ? 1 : chunks) : GWPB;
-    v.wgs = groups;
-  } else {            // GWPB independent waves per workgroup
-    v.nw = GWPB;
-    v.wgs = cdiv64(groups, GWPB);
-  }
-  return v;
-}
-
-template <int NCH, bool DEFORM = false>
-int launch_vec(KPParams P, int idx64, hipStream_t st) {
-  const bool fast = P.influence == MVK_INFL_LINEAR && P.aggregation == MVK_AGG_SUM;
-  const VecPlan v = plan_vec(P.Nq, P.H, P.Cin, DEFORM);
-  if (DEFORM) P.order = nullptr;
-  P.xcd_blocks = P.order != nullptr ? (int)v.wgs : 0;
-  dim3 grid((unsigned)v.wgs), block(64 * v.nw);
-#define LV(I64, F) hipLaunchKernelGGL((kpconv_gather_vec<NCH, I64, F, DEFORM>), grid, block, 0, st, P, v.LPP, v.PPW, v.HC)
-  if (idx64) {
-    if (fast) LV(true, true);
-    else LV(true, false);
-  } else {
-    if (fast) LV(false, true);
-    else LV(false, false);
-  }
-#undef LV
-  return 0;
-}
-
-// channel tiles per wave of the MFMA gather for rows of Cin channels (0: the layer stays on the vector kernels)
+// channel tiles per wave of the MFMA gather for rows of Cin channels (0: the lane = channel kernel)
 int mfma_tiles(int64_t Ns, int Cin, int K, int influence, int aggregation) {
   if (influence != MVK_INFL_LINEAR || aggregation != MVK_AGG_SUM || K > 16 || Cin < 1) return 0;
   if ((uint64_t)Ns * (uint64_t)Cin >= (1ull << 32) - 4096) return 0;
@@ -1168,7 +663,7 @@ extern "C" int mvk_kpconv_gather_fwd_ordered(const float* q, int64_t Nq, const f
   if (Nq == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   KPParams P{};
-  P.order = order;        // used by the vector kernels of rigid layers (5 <= Cin <= 512); the other kernels work in row order
+  P.order = order;        // read by the MFMA gather; the lane = channel kernel works in row order
   P.q = q; P.s = s; P.idx = idx; P.x = x; P.kp = kp; P.offsets = offsets; P.min_d2 = min_d2; P.min_arg = min_arg;
   P.A = A_out; P.Nq = Nq; P.Ns = Ns; P.H = H; P.Cin = Cin; P.K = K; P.extent = extent;
   P.influence = influence; P.aggregation = aggregation;
@@ -1176,38 +671,13 @@ extern "C" int mvk_kpconv_gather_fwd_ordered(const float* q, int64_t Nq, const f
     MVK_CHECK_HIP(hipMemsetAsync(A_out, 0, sizeof(float) * Nq * K * Cin, st));
     if (offsets == nullptr) return 0;
   }
+  // the aggregation on the matrix pipe (linear influence, sum aggregation, feature table < 2^32 elements), everything
+  // else one point per wave with lane = channel
   if (offsets != nullptr) {
     KPParams Pm = P;
     Pm.order = nullptr;           // (the deformable levels are the coarse ones: no work list)
-    if (launch_mfma<1>(Pm, idx64, st)) {
-      // (round 5: the deformable forward on the matrix pipe as well, KPM 1 of kpconv_gather_mfma)
-    } else if (Cin >= 13 && Cin <= 256) {          // 64 / ceil(Cin/4) <= DPPW points per wave
-      launch_vec<1, true>(P, idx64, st);
-    } else if (Cin > 256 && Cin <= 512) {
-      launch_vec<2, true>(P, idx64, st);
-    } else {
-      launch_lane_channel<0, true>(P, idx64, st);
-    }
-  } else if (Cin <= 4 && launch_mfma<0>(P, idx64, st)) {
-    // (narrow rows -- the first layer of the baseline / middle / late nets -- on the matrix pipe too: 21.7 against 28.8 us
-    // for 19 464 points x 4 channels; most of the 16 x 16 tile is idle, but the kernel's cost there is the geometry)
-  } else if (Cin <= 4) {
-    const bool fast = influence == MVK_INFL_LINEAR && aggregation == MVK_AGG_SUM;
-    dim3 grid((unsigned)cdiv64(Nq * 4, 256)), block(256);       // four lanes per point
-    if (idx64) {
-      if (fast) hipLaunchKernelGGL((kpconv_gather_small<true, true>), grid, block, 0, st, P);
-      else hipLaunchKernelGGL((kpconv_gather_small<true, false>), grid, block, 0, st, P);
-    } else {
-      if (fast) hipLaunchKernelGGL((kpconv_gather_small<false, true>), grid, block, 0, st, P);
-      else hipLaunchKernelGGL((kpconv_gather_small<false, false>), grid, block, 0, st, P);
-    }
-  } else if (launch_mfma<0>(P, idx64, st)) {
-    // (the aggregation on the matrix pipe: linear influence, sum aggregation, feature table < 2^32 elements)
-  } else if (Cin <= 256) {
-    launch_vec<1>(P, idx64, st);
-  } else if (Cin <= 512) {
-    launch_vec<2>(P, idx64, st);
-  } else {
+    if (!launch_mfma<1>(Pm, idx64, st)) launch_lane_channel<0, true>(P, idx64, st);
+  } else if (!launch_mfma<0>(P, idx64, st)) {
     launch_lane_channel<0, false>(P, idx64, st);
   }
   MVK_CHECK_HIP(hipGetLastError());
@@ -1275,24 +745,18 @@ extern "C" int mvk_kpconv_scatter_bwd(const float* q, int64_t Nq, const float* s
 }
 
 // Launch geometry mvk_kpconv_gather_fwd uses for a layer (elem_bytes: 4, the f32 rows -- the only row type)
-// with linear influence and sum aggregation: out[0..7] = lanes per point, points per wave, channel tiles per wave
-// (MFMA gather; 0 on the vector kernel), first sharing workgroup (0: every workgroup shares its points among its
-// waves; the workgroup count, or -1 on the MFMA gather: none does), waves per workgroup, workgroups, grid threads
-// (what a kernel trace reports), 1 = the MFMA gather. out[5] = 0: the layer runs on another kernel (one point per
-// wave, or one point per four lanes for rows of <= 4 channels).
+// with linear influence and sum aggregation. On the MFMA gather out[0..7] = 64 (lanes per point), 1 (point per wave),
+// channel tiles per wave, 0 (the four waves of a workgroup share one point) or -1 (one point each), 4 (waves per
+// workgroup), workgroups, grid threads (what a kernel trace reports), 1. All eight are 0 when the layer runs on the
+// lane = channel kernel (one point per wave) or launches nothing.
 extern "C" int mvk_kpconv_gather_plan(int64_t Nq, int64_t Ns, int H, int Cin, int elem_bytes, int deformable,
                                       int64_t* out) {
   MVK_REQUIRE(out != nullptr && elem_bytes == 4, "kpconv plan: bad arguments (feature rows are f32: elem_bytes 4)");
   for (int i = 0; i < 8; ++i) out[i] = 0;
   const MfmaPlan mp = plan_mfma(Nq, Ns, H, Cin, 15, MVK_INFL_LINEAR, MVK_AGG_SUM, deformable != 0);
-  if (Nq > 0 && mp.T > 0) {        // the MFMA gather: four waves per workgroup (one point each, or sharing one), channel blocks in gridDim.y
+  if (Nq > 0 && mp.T > 0) {        // four waves per workgroup (one point each, or sharing one), channel blocks in gridDim.y
     out[0] = 64; out[1] = 1; out[2] = mp.T; out[3] = mp.SW > 1 ? 0 : -1; out[4] = 4; out[5] = mp.wgs * mp.blocks_y;
     out[6] = out[5] * 256; out[7] = 1;
-    return 0;
   }
-  if (Nq <= 0 || Cin <= 0 || Cin > 512 || (deformable && Cin < 13) || (!deformable && Cin <= 4)) return 0;      // (one point per 4 lanes: kpconv_gather_small)
-  const VecPlan v = plan_vec(Nq, H, Cin, deformable != 0);
-  out[0] = v.LPP; out[1] = v.PPW; out[3] = deformable ? 0 : v.wgs; out[4] = v.nw; out[5] = v.wgs;
-  out[6] = v.wgs * 64 * v.nw;
   return 0;
 }

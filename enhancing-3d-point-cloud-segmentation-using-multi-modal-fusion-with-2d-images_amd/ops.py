@@ -183,10 +183,10 @@ def gemm_plan(M, N, Kd, split_k=None, want_stats=False):
 
 
 def kpconv_gather_plan(Nq, Ns, H, Cin, elem_bytes=4, deformable=False):
-    """Launch geometry of the gather kernel for a (linear, sum) layer (mvk_kpconv_gather_plan): dict with the
-    lanes per point, points per wave, 'rows_per_batch' (the MFMA gather's channel tiles per wave; 0 on the vector
-    kernel), first sharing workgroup, waves per workgroup, workgroups and grid threads; 'workgroups' 0 means the layer
-    runs on the one-point-per-wave kernel."""
+    """Launch geometry of the MFMA gather for a (linear, sum) layer (mvk_kpconv_gather_plan): 'mfma' 1,
+    'lanes_per_point' 64, 'points_per_wave' 1, 'rows_per_batch' (its channel tiles per wave), 'first_sharing_workgroup'
+    (0: the four waves of a workgroup share one point, -1: one point each), 'waves_per_workgroup' 4, 'workgroups' and
+    'grid_threads'. Every value is 0 when the layer runs on the lane = channel kernel, one point per wave."""
     out = (C.c_int64 * 8)()
     check(lib().mvk_kpconv_gather_plan(int(Nq), int(Ns), int(H), int(Cin), int(elem_bytes), int(bool(deformable)), out))
     keys = ("lanes_per_point", "points_per_wave", "rows_per_batch", "first_sharing_workgroup", "waves_per_workgroup",
@@ -390,29 +390,12 @@ def profile_collect_contraction():
     return out
 
 
-def _gather_kernel_name(Cin, deform):
-    if deform:
-        if 13 <= Cin <= 512:
-            lpp = min((Cin + 3) // 4, 64)
-            return "kpconv_gather_vec<NCH=%d,deform>(LPP=%d,PPW=%d)" % (1 if Cin <= 256 else 2, lpp, 64 // lpp)
-        return "kpconv_lane_channel<fwd,deform>"
-    if Cin <= 4:
-        return "kpconv_gather_small(4 lanes per point)"
-    if Cin <= 512:
-        lpp = min((Cin + 3) // 4, 64)
-        return "kpconv_gather_vec<NCH=%d>(LPP=%d,PPW=%d)" % (1 if Cin <= 256 else 2, lpp, 64 // lpp)
-    return "kpconv_lane_channel<fwd>"
-
-
-def _gather_kernel_label(Nq, Ns, H, Cin, deform, elem_bytes=4):
-    """Kernel name with the launch geometry the library actually uses (mvk_kpconv_gather_plan)."""
-    p = kpconv_gather_plan(Nq, Ns, H, Cin, elem_bytes, deform)
-    if p["workgroups"] == 0:
-        return _gather_kernel_name(Cin, deform)
-    if p.get("mfma"):
+def _gather_kernel_label(Nq, Ns, H, Cin, deform, fast=True):
+    """Name of the kernel mvk_kpconv_gather_fwd launches (fast: linear influence and sum aggregation)."""
+    p = kpconv_gather_plan(Nq, Ns, H, Cin, 4, deform)
+    if fast and p["mfma"]:
         return "kpconv_gather_mfma<T=%d>(1 point per wave)" % p["rows_per_batch"]
-    return "kpconv_gather_vec<NCH=%d%s>(LPP=%d,PPW=%d)" % (1 if Cin <= 256 else 2, ",deform" if deform else "",
-                                                           p["lanes_per_point"], p["points_per_wave"])
+    return "kpconv_lane_channel<fwd,deform>" if deform else "kpconv_lane_channel<fwd>"
 
 
 def profile_collect(h_eff=None):
@@ -467,7 +450,7 @@ def kpconv_gather(q, s, idx, x, kp, extent, influence="linear", aggregation="sum
                                               _p(offsets), _p(min_d2), _p(min_arg), _p(A), _p(order), _stream()))
     if _PROF["on"]:
         e1.record()
-        name = _gather_kernel_label(Nq, Ns, H, Cin, offsets is not None)
+        name = _gather_kernel_label(Nq, Ns, H, Cin, offsets is not None, (influence, aggregation) == ("linear", "sum"))
         if tag:         # the gather-form feature gradient: its own class, with the mean length of ITS (reverse) rows
             name += tag
             _PROF.setdefault("h_eff", {})[(Nq, Ns, H)] = float((idx < Ns).sum().item()) / max(Nq, 1)

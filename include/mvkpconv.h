@@ -63,9 +63,9 @@ int mvk_kpconv_gather_fwd(const float* q, int64_t Nq, const float* s, int64_t Ns
                           int32_t* min_arg /* [Nq,K] or NULL: neighbour column of the first entry attaining min_d2 */,
                           float* A_out, void* stream);
 
-/* The same with a work list: order [Nq] int32 = a permutation of 0 .. Nq-1 (NULL = row order). The vector kernels of
- * rigid layers (5 <= Cin <= 512) process the points in that order -- consecutive entries share a wave, consecutive
- * waves an XCD -- and write every result in the point's own row: A_out is what mvk_kpconv_gather_fwd writes, whatever
+/* The same with a work list: order [Nq] int32 = a permutation of 0 .. Nq-1 (NULL = row order). The MFMA gather of
+ * rigid layers (linear influence, sum aggregation) processes the points in that order -- consecutive entries share a
+ * workgroup, consecutive workgroups an XCD -- and writes every result in the point's own row: A_out is what mvk_kpconv_gather_fwd writes, whatever
  * the permutation (a spatially sorted one keeps the neighbour rows a workgroup pulls inside its XCD's L2). Entries
  * outside [0, Nq) or repeated entries are the caller's error (rows written twice / not at all). */
 int mvk_kpconv_gather_fwd_ordered(const float* q, int64_t Nq, const float* s, int64_t Ns,
@@ -77,11 +77,11 @@ int mvk_kpconv_gather_fwd_ordered(const float* q, int64_t Nq, const float* s, in
 /* Launch geometry mvk_kpconv_gather_fwd uses for a layer with linear influence and sum aggregation
  * (elem_bytes: 4 -- feature rows are f32; the fp16-feature mode of rounds 2-4 left the tree in round 5, DESIGN.md 4.7;
  * host only, no GPU call):
- * out[0..6] = lanes per point, points per wave, 0 on the vector kernel (see out[7]), first workgroup whose waves
- * share their points (0: all of them; the workgroup count, or -1 on the MFMA gather: none), waves per workgroup,
- * workgroups, grid threads (the figure a kernel trace reports). out[5] = 0: the layer runs on another kernel (one point per wave;
- * one point per lane for rows of <= 4 channels). out[7] (ABI 7) = 1: the MFMA gather (kpconv_gather_mfma, round 5: layers
- * with linear influence and sum aggregation -- one wave per point, out[2] = its 16-channel accumulator tiles), 0: the vector kernel. */
+ * on the MFMA gather (kpconv_gather_mfma, one wave per point) out[0..7] = 64, 1, its 16-channel accumulator tiles per
+ * wave, 0 (the four waves of a workgroup share one point) or -1 (one point each), 4 (waves per workgroup), workgroups,
+ * grid threads (the figure a kernel trace reports), 1. Every other layer -- a feature table of 2^32 - 4096 elements or
+ * more -- runs on kpconv_lane_channel, one point per wave, and so does every other influence / aggregation whatever
+ * this plan says: all eight are 0 (out[5] = 0: "another kernel, one point per wave"; also for Nq = 0). */
 int mvk_kpconv_gather_plan(int64_t Nq, int64_t Ns, int H, int Cin, int elem_bytes, int deformable, int64_t* out /* [8] */);
 
 /* Gather-form feature gradient of a DEFORMABLE KPConv (round 5): A2 [Ns, K, C] = the forward aggregation over the

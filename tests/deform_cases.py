@@ -42,7 +42,7 @@ CASES = [
     _c("m64c", 64, 64, 117, Nq=48, influence="constant"),
     _c("m68", 68, 68, 130, Nq=40),                                         # strided; second c0 iteration holds 4 channels
     _c("m256", 256, 16, 300, Nq=24, side=0.15),                            # 4 full c0 iterations, 5 chunks over 4 waves
-    _c("m260g", 260, 8, 70, Nq=24, influence="gaussian"),                  # forward on kpconv_gather_vec<2, DEFORM>
+    _c("m260g", 260, 8, 70, Nq=24, influence="gaussian"),                  # forward on kpconv_lane_channel<8, .., 0, DEFORM>
     _c("m128", 128, 32, 1030, Nq=20, idx64=True, mod=True, side=0.12),     # list capacity 320 per wave
     _c("m8k3", 8, 8, 40, Nq=16, K=3, side=0.15),
     # ---- vector offset gradient
@@ -132,10 +132,6 @@ def dispatch(c):
     d["list_cap"] = max(64, (chunks + d["wpb"] - 1) // d["wpb"] * 64)
     if c.influence == "linear":
         d["forward"] = "mfma<KPM 1>"
-    elif 13 <= c.cin <= 256:
-        d["forward"] = "vec<1, DEFORM>"
-    elif 256 < c.cin <= 512:
-        d["forward"] = "vec<2, DEFORM>"
     else:
         d["forward"] = "lane_channel<0, DEFORM> x %d" % ((c.cin + 511) // 512)
     d["scatter"] = "lane_channel<1, DEFORM>%s x %d" % (" 4 waves" if c.H > 64 else "", (c.cin + 511) // 512)
@@ -173,7 +169,7 @@ ROW_TOL = 1e-4       # the per-row bound (row_err)
 
 def shadow_rows(name):
     """Rows of shadow entries only: their min_d2 (~3e12) and d_offsets (~2e6 g_min_d2) are compared on their own scale
-    (as test_kpconv_deformable_vector_gather_closest_vs_numpy_oracle does) and do not set the floor of the other rows."""
+    (as test_kpconv_deformable_gather_closest_vs_numpy_oracle does) and do not set the floor of the other rows."""
     i = make_inputs(name)
     return (i.idx >= i.s.shape[0]).all(1)
 

@@ -132,8 +132,7 @@ def test_case_table_covers_the_dispatch_branches():
     both = {key(c) for c in dc.CASES if c.mod} & {key(c) for c in dc.CASES if not c.mod}
     assert len(both) >= 4 and any(k[3] != k[4] for k in both)
     assert {5, 8, 20, 64, 68} <= {c.cout for c in dc.CASES if D[c.name]["gather_dx"]}
-    assert {"mfma<KPM 1>", "vec<1, DEFORM>", "vec<2, DEFORM>", "lane_channel<0, DEFORM> x 1",
-            "lane_channel<0, DEFORM> x 3"} <= {D[n]["forward"] for n in D}
+    assert {"mfma<KPM 1>", "lane_channel<0, DEFORM> x 1", "lane_channel<0, DEFORM> x 3"} <= {D[n]["forward"] for n in D}
     assert all(12 <= c.Nq <= 64 or c.Nq == 1025 for c in dc.CASES)
 
 

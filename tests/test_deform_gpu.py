@@ -102,7 +102,7 @@ def test_deformable_aggregate_and_a_path_offset_gradient(ops, name):
 
 
 def test_deformable_closest_backward_is_a_loud_error(ops):
-    """Deformable + `closest` aggregation has a forward (kpconv_gather_vec<DEFORM>) and no offset-gradient path: the
+    """Deformable + `closest` aggregation has a forward (kpconv_lane_channel<.., fwd, DEFORM>) and no offset-gradient path: the
     backward raises on the host."""
     i = dc.make_inputs("m20")
     x, off = T(i.x).requires_grad_(True), T(i.offsets).requires_grad_(True)

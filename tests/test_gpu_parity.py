@@ -305,7 +305,7 @@ VARIANT_SHAPES = [(1, 5, 9), (4, 32, 17), (8, 8, 70), (20, 12, 33), (68, 64, 40)
                   (128, 16, 25), (256, 8, 64), (512, 4, 10), (516, 4, 6), (1040, 3, 5),
                   (2, 6, 130), (130, 16, 150), (600, 4, 130), (30, 5, 260),
                   (61, 8, 40), (62, 8, 16), (67, 8, 33), (129, 8, 20), (255, 4, 70)]
-# (linear, sum) runs on the MFMA gather wherever it can; the other two modes keep kpconv_gather_vec (5 <= Cin <= 512)
+# (linear, sum) runs on the MFMA gather wherever it can; the other two modes run on kpconv_lane_channel (any Cin)
 VARIANT_MODES = [("linear", "sum"), ("gaussian", "sum"), ("linear", "closest")]
 
 
@@ -313,10 +313,10 @@ VARIANT_MODES = [("linear", "sum"), ("gaussian", "sum"), ("linear", "closest")]
     pytest.param(*shape, *mode, id="-".join(str(v) for v in (shape if mode == VARIANT_MODES[0] else shape + mode)))
     for mode in VARIANT_MODES for shape in VARIANT_SHAPES])
 def test_kpconv_every_kernel_variant_vs_numpy_oracle(ops, cin, cout, H, influence, agg):
-    """Seeded inputs through every gather / scatter template instantiation (LPP = 1..64, NCH = 1, 2 of the vector
-    gather under the gaussian influence and the `closest` aggregation, the MFMA gather's tile counts under linear / sum,
-    the generic lane = channel kernel and its > 512-channel multi-launch path, the one-lane-per-point kernel for rows
-    of <= 4 channels, the four-waves-per-point scatter of rows with more than 64 neighbour columns) against the float64
+    """Seeded inputs through every gather / scatter template instantiation (the MFMA gather's tile counts under
+    linear / sum; NSLOT = 1, 2, 4, 8 of the generic lane = channel kernel and its > 512-channel multi-launch path as the
+    forward under the gaussian influence and the `closest` aggregation, rows of <= 4 channels included, and as the
+    scatter; the four-waves-per-point scatter of rows with more than 64 neighbour columns) against the float64
     numpy restatement; includes shadow neighbours, empty rows and a ragged last chunk."""
     from oracle import npref
     rng = np.random.default_rng(cin * 131 + H)
@@ -341,11 +341,11 @@ def test_kpconv_every_kernel_variant_vs_numpy_oracle(ops, cin, cout, H, influenc
     assert rel_err(Wt.grad.cpu().numpy(), dW) < FP_TOL
 
 
-@pytest.mark.parametrize("cin,H", [(20, 70), (61, 150), (300, 70)])
-def test_kpconv_deformable_vector_gather_closest_vs_numpy_oracle(ops, cin, H):
-    """Deformable layers with the `closest` aggregation run on kpconv_gather_vec<DEFORM> (the MFMA gather takes
-    linear / sum only): LPP 5 / 16 / 64, NCH 1 and 2, a ragged last quad (61), a last point group that is not full
-    (50 points) and more than one neighbour chunk per wave, so that the waves of a workgroup share their points.
+@pytest.mark.parametrize("cin,H", [(20, 70), (61, 150), (300, 70), (100, 70), (200, 40)])
+def test_kpconv_deformable_gather_closest_vs_numpy_oracle(ops, cin, H):
+    """Deformable layers with the `closest` aggregation run on kpconv_lane_channel<NSLOT, .., fwd, DEFORM> (the MFMA
+    gather takes linear / sum only): NSLOT 1 (20 and 61 channels: a partly filled slot), 8 (300), 2 (100) and 4 (200),
+    rows of one, two and three 64-column chunks with a ragged last one.
     Aggregate and min_d2 (over real and shadow entries) against the float64 numpy restatement; linear influence, where
     the reference's in-range filter drops weights that are exactly zero."""
     from oracle import npref
@@ -375,18 +375,11 @@ def test_kpconv_deformable_vector_gather_closest_vs_numpy_oracle(ops, cin, H):
 
 @pytest.mark.parametrize("Nq,cin,H", [(40000, 32, 12), (70000, 66, 30), (17000, 64, 40), (21000, 128, 70), (19000, 66, 40),
                                       (17500, 65, 20)])
-def test_kpconv_gather_launches_with_sharing_workgroups_vs_numpy_oracle(ops, Nq, cin, H):
-    """Launches large enough that their last partial round of waves runs as sharing workgroups (the waves of a workgroup
-    split the neighbour chunks of ONE point group and wave 0 adds the partial aggregates, csrc/kpconv.hip): the
-    aggregate of every region of the launch -- independent waves, sharing workgroups, the ragged last group --
-    against the float64 numpy restatement."""
+def test_kpconv_gather_large_launches_vs_numpy_oracle(ops, Nq, cin, H):
+    """Launches of tens of thousands of points on the MFMA gather (one wave per point): the aggregate of every region
+    of the launch -- its first rows, the rows an eighth of the way in, the ragged last workgroup, random rows; shadow
+    entries in the middle of rows -- against the float64 numpy restatement."""
     from oracle import npref
-    plan = ops.kpconv_gather_plan(Nq, 3000, H, cin)
-    if plan["mfma"]:
-        # round 5: rigid f32 layers run on the MFMA gather (one wave per point, no sharing workgroups) -- the same rows
-        # are checked all the same (shadow entries in the middle of rows, ragged last workgroup)
-        plan = dict(plan, first_sharing_workgroup=Nq // 8, points_per_wave=1)
-    assert 0 < plan["first_sharing_workgroup"] < plan["workgroups"], plan       # the case this test is about
     rng = np.random.default_rng(Nq + cin)
     Ns, K = 3000, 15
     q = (rng.random((Nq, 3)) * 0.3).astype(np.float32)
@@ -396,9 +389,8 @@ def test_kpconv_gather_launches_with_sharing_workgroups_vs_numpy_oracle(ops, Nq,
     x = rng.normal(size=(Ns, cin)).astype(np.float32)
     kp = (rng.normal(size=(K, 3)) * 0.05).astype(np.float32)
     A = ops.kpconv_gather(T(q), T(s), T(idx), T(x), T(kp), 0.06)[0].cpu().numpy()
-    ppw = plan["points_per_wave"]
-    first_shared = plan["first_sharing_workgroup"] * 4 * ppw
-    rows = np.unique(np.concatenate([np.arange(0, 64), np.arange(first_shared - 64, first_shared + 64),
+    eighth = (Nq // 8) * 4
+    rows = np.unique(np.concatenate([np.arange(0, 64), np.arange(eighth - 64, eighth + 64),
                                      np.arange(Nq - 64, Nq), rng.integers(0, Nq, 512)]))
     W1 = np.zeros((K, cin, 1))
     _, want, _ = npref.kpconv_forward(q[rows].astype(np.float64), s.astype(np.float64), idx[rows].astype(np.int64),
@@ -408,10 +400,9 @@ def test_kpconv_gather_launches_with_sharing_workgroups_vs_numpy_oracle(ops, Nq,
 
 @pytest.mark.parametrize("Nq,cin,H", [(3001, 64, 30), (19000, 66, 40), (21000, 128, 30), (9000, 300, 20), (5000, 3, 20)])
 def test_kpconv_gather_with_a_work_list_writes_the_rows_of_the_plain_gather(ops, Nq, cin, H):
-    """mvk_kpconv_gather_fwd_ordered: the work list only changes which wave (and which XCD) works on a point. Launches
-    without a mix of independent waves and sharing workgroups (every point summed in the same way whatever its slot)
-    must give the same BITS as the row order; mixed launches (a point's slot decides whether one wave or four sum its
-    neighbours) within the rounding of that sum; the layer as a whole (ops.kpconv) likewise."""
+    """mvk_kpconv_gather_fwd_ordered: the work list only changes which wave (and which XCD) works on a point. Every
+    point is summed in the same way whatever its slot, so every work list must give the same BITS as the row order;
+    the layer as a whole (ops.kpconv) to 2e-6."""
     rng = np.random.default_rng(Nq + cin)
     Ns, K = Nq, 15
     s = (rng.random((Ns, 3)) * 0.6).astype(np.float32)
@@ -422,18 +413,12 @@ def test_kpconv_gather_with_a_work_list_writes_the_rows_of_the_plain_gather(ops,
     kp = T((rng.normal(size=(K, 3)) * 0.05).astype(np.float32))
     qt, st, it = T(q), T(s), T(idx)
     plain = ops.kpconv_gather(qt, st, it, x, kp, 0.06)[0]
-    plan = ops.kpconv_gather_plan(Nq, Ns, H, cin)
-    mixed = 0 < plan["first_sharing_workgroup"] < plan["workgroups"]
     cells = np.floor(s / 0.06).astype(np.int64)
     orders = {"random": rng.permutation(Nq), "reversed": np.arange(Nq)[::-1].copy(),
               "cells": np.lexsort((cells[:, 0], cells[:, 1], cells[:, 2]))}
     for name, o in orders.items():
         got = ops.kpconv_gather(qt, st, it, x, kp, 0.06, order=T(o.astype(np.int32)))[0]
-        if mixed:
-            err = float((got - plain).abs().max() / plain.abs().max())
-            check_err("gather with the %s work list vs the row order (Nq %d, Cin %d, mixed launch)" % (name, Nq, cin), err, 2e-6)
-        else:
-            assert torch.equal(got, plain), (name, plan)
+        assert torch.equal(got, plain), (name, Nq, cin)
     with pytest.raises(RuntimeError):
         ops.kpconv_gather(qt, st, it, x, kp, 0.06, order=T(np.arange(Nq - 1, dtype=np.int32)))
     if cin == 66:
@@ -1992,8 +1977,8 @@ def test_regulariser_of_all_layers_as_one_node_equals_the_per_layer_sum(ops):
 @pytest.mark.parametrize("influence,agg", [("gaussian", "sum"), ("constant", "sum"), ("linear", "closest"), ("gaussian", "closest")])
 @pytest.mark.parametrize("cin,idt", [(2, torch.int32), (4, torch.int64), (3, torch.int32)])
 def test_kpconv_small_row_kernel_other_influences_vs_numpy_oracle(ops, cin, idt, influence, agg):
-    """kpconv_gather_small (rows of <= 4 channels, four lanes per point) with the non-default influence / aggregation
-    modes and both index widths, a point count that is not a multiple of the wave."""
+    """Rows of <= 4 channels with the non-default influence / aggregation modes, which kpconv_lane_channel<1, .., fwd>
+    serves (one wave per point, two to four of its lanes hold a channel), and both index widths."""
     from oracle import npref
     rng = np.random.default_rng(cin * 7 + len(influence) + len(agg))
     Nq, Ns, K, H = 1001, 777, 15, 23

@@ -51,6 +51,8 @@ def test_gather_launch_plan_is_a_host_function():
     assert d["mfma"] == 1 and d["first_sharing_workgroup"] == 0 and d["workgroups"] == 750 and d["waves_per_workgroup"] == 4
     n = ops.kpconv_gather_plan(100, 100, 20, 2)                                # narrow rows: two tiles, mostly idle
     assert n["mfma"] == 1 and n["rows_per_batch"] == 2 and n["workgroups"] == 25
+    z = ops.kpconv_gather_plan(1000, 70_000_000, 20, 64)      # a table of >= 2^32 - 4096 elements: the lane = channel kernel
+    assert len(z) == 8 and not any(z.values()), z
     with pytest.raises(RuntimeError):
         ops.kpconv_gather_plan(100, 100, 20, 64, elem_bytes=2)                # the fp16-feature mode left the tree (round 5)
 
@@ -398,7 +400,7 @@ def test_bench_result_line_is_bounded():
     bench = importlib.import_module("bench")
     prof = {}
     for i in range(120):            # 120 distinct launch shapes, as the random grid orientation produces
-        prof[("k", i)] = {"kernel": "kpconv_gather_vec<NCH=1>(LPP=16,PPW=4,+2 trailing channels)", "launches": 16,
+        prof[("k", i)] = {"kernel": "kpconv_gather_mfma<T=5>(1 point per wave)[dx of a deformable layer]", "launches": 16,
                           "total_ms": 1.0 + (i == 0), "each_ms": [0.0671234567] * 16, "bytes_per_launch": 309427088.123,
                           "shape": {"Nq": 19464 - i, "Ns": 19464, "H": 58 - i % 5, "H_eff": 42.590731607069465, "Cin": 66, "K": 15}}
     bench.pmc_traffic = lambda best: (205634042.0, "r02_pmc_gather.json (python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline)")

@@ -12,7 +12,7 @@ one() {
   { echo "# python3 bench.py --no-eager-line --steps 20 --warmup 3 --no-cpu-baseline $* (rocprofv3 --kernel-trace --stats)"
     cat $R/gpurun_out/steady_$name.txt
     echo; echo "# kernels_by_grid (second trace of the same command, 10 steps): per (kernel, grid) launches and average duration"
-    for k in kpconv_gather_mfma kpconv_gather_vec kpconv_gather_small kpconv_lane_channel kpconv_deform nb_query rev_ knn_pruned subsample_cloud; do
+    for k in kpconv_gather_mfma kpconv_lane_channel kpconv_deform nb_query rev_ knn_pruned subsample_cloud; do
       echo "== $k"; python3 $R/tools/trace_by_grid.py $F $k | head -14
     done
     cd $R
