@@ -778,6 +778,8 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_grouped(const GroupEntry* _
 
 struct Plan {
   int pm, qn, narrow, split;
+  int64_t tm() const { return narrow ? 64 * pm : 16 * pm; }       // rows and columns of a workgroup's tile
+  int64_t tn() const { return narrow ? 16 * qn : 64 * qn; }
 };
 
 // Arena of the ordered split reductions (mvk_gemm_split_arena): the host layer hands over one large slot buffer and one
@@ -874,9 +876,8 @@ Plan plan_gemm(int64_t M, int64_t N, int64_t Kd, int split_req, bool want_stats)
   const int narrow = N <= 32 ? 1 : 0;
   // with statistics: 64-row tiles (one partial per 64 rows keeps the BatchNorm's reduction of the partials short)
   const int pm = narrow ? 1 : (want_stats ? 4 : 2), qn = narrow ? (N <= 16 ? 1 : 2) : 1;
-  const int64_t tm = narrow ? 64 * pm : 16 * pm, tn = narrow ? 16 * qn : 64 * qn;
-  const int64_t tiles = cdiv64(M, tm) * cdiv64(N, tn), ksteps = cdiv64(Kd, BK);
   Plan best{pm, qn, narrow, 1};
+  const int64_t tiles = cdiv64(M, best.tm()) * cdiv64(N, best.tn()), ksteps = cdiv64(Kd, BK);
   double best_t = 1e300, t1 = 1e300;
   for (int split = 1; split <= 64; ++split) {
     if (split_req > 0 && split != split_req) continue;
@@ -959,11 +960,30 @@ void pair_widen(Plan& a, const Plan& b, int64_t Kd) {
   }
 }
 
-void no_bn_fold(GemmArgs& a) {
-  a.fin_cnt = nullptr; a.fin_gy = 0; a.fin_eps = 0.f; a.fin_momentum = 0.f; a.fin_mean = nullptr; a.fin_invstd = nullptr;
-  a.fin_rmean = nullptr; a.fin_rvar = nullptr; a.fin_nbt = nullptr;
-  a.ax_mean = nullptr; a.ax_invstd = nullptr; a.ax_gamma = nullptr; a.ax_beta = nullptr; a.ax_slope = 1.f;
-  a.ax_nvalid = nullptr; a.ax_out = nullptr;
+// floats per load of an operand at p whose rows are ld floats apart: 4 / 2 need every row 16- / 8-byte aligned
+int vec_width(const void* p, int64_t ld) {
+  return ((ld % 4 == 0) && ((uintptr_t)p % 16 == 0)) ? 4 : ((ld % 2 == 0) && ((uintptr_t)p % 8 == 0)) ? 2 : 1;
+}
+
+// The split a reduction of Kd really gets when `split` is asked for: whole k-tiles per workgroup, no empty workgroup.
+// The plan exports and the launches both go through here.
+struct KSplit { int n; int64_t k_per_split; };
+KSplit clamp_split(int64_t Kd, int split) {
+  const int64_t ksteps = cdiv64(Kd, BK);
+  if (split > ksteps) split = (int)ksteps;
+  const int64_t k_per_split = cdiv64(ksteps, split) * BK;
+  return {(int)cdiv64(Kd, k_per_split), k_per_split};
+}
+
+// The arguments of one plain product C = A . B, every extension off: an entry point sets what is its own on top of this
+GemmArgs make_args(const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t Kd, int64_t lda, int64_t ldb,
+                   KSplit ks) {
+  GemmArgs a{};
+  a.A = A; a.B = B; a.C = C; a.M = M; a.N = N; a.Kd = Kd;
+  a.lda = lda; a.ldb = ldb; a.vecA = vec_width(A, lda); a.vecB = vec_width(B, ldb);
+  a.k_per_split = ks.k_per_split; a.atomic_out = ks.n > 1; a.det_nsplit = ks.n;
+  a.act_slope = 1.f; a.ax_slope = 1.f; a.vecA2 = 1; a.vecB2 = 1; a.seg_shift = -1;      // the neutral values that are not zero
+  return a;
 }
 
 // the producer's half of a folded BatchNorm (GemmArgs (a)); gy = row tiles of the launch
@@ -979,32 +999,112 @@ int set_finish(GemmArgs& a, const mvk_bn_finish* fin, int64_t gy) {
   return 0;
 }
 
-// fills the arguments of one product like mvk_gemm_f32_ex does; returns its split
-int fill_args(GemmArgs& a, const Plan& p, const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t Kd,
-              int transA, int transB, float* bn_part, const int32_t* n_valid) {
-  int split = p.split;
-  const int64_t ksteps = cdiv64(Kd, BK);
-  if (split > ksteps) split = (int)ksteps;
-  const int64_t k_per_split = cdiv64(ksteps, split) * BK;
-  split = (int)cdiv64(Kd, k_per_split);
-  a.A = A; a.B = B; a.C = C; a.M = M; a.N = N; a.Kd = Kd;
-  a.lda = transA ? M : Kd;
-  a.ldb = transB ? Kd : N;
-  a.k_per_split = k_per_split;
-  a.atomic_out = split > 1;
-  a.accumulate = 0;
-  a.vecA = ((a.lda % 4 == 0) && ((uintptr_t)A % 16 == 0)) ? 4 : ((a.lda % 2 == 0) && ((uintptr_t)A % 8 == 0)) ? 2 : 1;
-  a.vecB = ((a.ldb % 4 == 0) && ((uintptr_t)B % 16 == 0)) ? 4 : ((a.ldb % 2 == 0) && ((uintptr_t)B % 8 == 0)) ? 2 : 1;
-  a.bn_part = bn_part;
-  a.n_valid = n_valid;
-  a.bias = nullptr;
-  a.act_slope = 1.f;
-  a.A2 = nullptr; a.B2 = nullptr; a.Kd2 = 0; a.lda2 = 0; a.ldb2 = 0; a.vecA2 = 1; a.vecB2 = 1;
-  a.sc_idx = nullptr; a.sc_idx64 = 0; a.sc_c1 = 0; a.sc_stride = 0; a.sc_ns = 0; a.sc_dst = nullptr; a.sc_rest = nullptr;
-  a.det_ws = nullptr; a.det_cnt = nullptr; a.det_gx = 0; a.det_nsplit = split;
-  a.seg_shift = -1; a.seg_extra = 0;
-  no_bn_fold(a);
-  return split;
+struct ScatterOut {
+  const void* idx;
+  int idx64, c1;
+  int64_t stride, ns;
+  float* dst;
+  float* rest;
+};
+
+// what a single product may ask for beyond C = op(A) . op(B); every extern "C" wrapper names the few fields it sets
+struct GemmOpts {
+  int accumulate = 0, split_k = 0;
+  float* bn_part = nullptr;
+  const int32_t* n_valid = nullptr;
+  const float* bias = nullptr;
+  float act_slope = 1.f;
+  const ScatterOut* scatter = nullptr;
+  int seg_shift = -1;
+  int64_t seg_extra = 0, ldb = 0;
+  const mvk_bn_finish* fin = nullptr;
+  const mvk_a_transform* ax = nullptr;
+};
+
+// one product: behind every mvk_gemm_f32* entry point of a single product
+int gemm_run(const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t Kd, int transA, int transB,
+             const GemmOpts& o, void* stream) {
+  MVK_REQUIRE(M >= 0 && N >= 0 && Kd >= 0, "gemm: negative size");
+  if (M == 0 || N == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  MVK_REQUIRE(!(o.bn_part && (o.accumulate || Kd == 0)), "gemm: BatchNorm statistics need a plain store of a non-empty product");
+  if (Kd == 0) {
+    if (!o.accumulate && o.split_k <= 1) MVK_CHECK_HIP(hipMemsetAsync(C, 0, sizeof(float) * M * N, st));
+    return 0;
+  }
+  MVK_REQUIRE(!(o.bn_part && o.split_k > 1 && !ordered_splits()), "gemm: BatchNorm statistics need an unsplit (or ordered) reduction");
+  const Plan p = plan_gemm(M, N, Kd, (o.bn_part && !ordered_splits()) ? 1 : (o.split_k > 0 ? o.split_k : 0), o.bn_part != nullptr);
+  const KSplit ks = clamp_split(Kd, p.split);
+  // o.ldb: B = a column block of a wider matrix
+  GemmArgs a = make_args(A, B, C, M, N, Kd, transA ? M : Kd, o.ldb > 0 ? o.ldb : (transB ? Kd : N), ks);
+  if (o.seg_shift >= 0) {
+    a.ldb = (int64_t)1 << o.seg_shift;        // rows of W[k]: Cout floats
+    a.vecB = ((uintptr_t)B % 16 == 0 && o.seg_extra % 4 == 0) ? 4 : 1;
+  }
+  a.accumulate = o.accumulate; a.bn_part = o.bn_part; a.n_valid = o.n_valid; a.bias = o.bias; a.act_slope = o.act_slope;
+  a.seg_shift = o.seg_shift; a.seg_extra = o.seg_extra;
+  if (o.scatter) {
+    a.sc_idx = o.scatter->idx; a.sc_idx64 = o.scatter->idx64; a.sc_c1 = o.scatter->c1; a.sc_stride = o.scatter->stride;
+    a.sc_ns = o.scatter->ns; a.sc_dst = o.scatter->dst; a.sc_rest = o.scatter->rest;
+  }
+  MVK_REQUIRE(cdiv64(M, p.tm()) < 65536 && ks.n < 65536, "gemm: grid too large");
+  dim3 grid((unsigned)cdiv64(N, p.tn()), (unsigned)cdiv64(M, p.tm()), (unsigned)ks.n);
+  MVK_ORDERED(make_ordered(st, a, ks.n, (int)grid.x, grid.y, p.tm(), p.tn()));
+  MVK_REQUIRE(!(o.bn_part && ks.n > 1 && !a.det_ws), "gemm: BatchNorm statistics of a split product need the ordered reduction");
+  if (int e = set_finish(a, o.fin, grid.y)) return e;
+  if (const mvk_a_transform* ax = o.ax) {
+    // the consumer's half of a folded BatchNorm (GemmArgs (b)): wide NT tiles, the workgroup's k-range inside the table
+    MVK_REQUIRE(!transA && transB && !p.narrow && p.qn == 1 && (p.pm == 2 || p.pm == 4) && ks.k_per_split <= XF_KMAX && !o.scatter &&
+                    o.seg_shift < 0 && ax->mean && ax->invstd && ax->gamma && ax->beta && ax->slope > 0.f,
+                "gemm: the operand transform needs an NT product of more than 32 columns with k-ranges <= %d", XF_KMAX);
+    a.ax_mean = ax->mean; a.ax_invstd = ax->invstd; a.ax_gamma = ax->gamma; a.ax_beta = ax->beta; a.ax_slope = ax->slope;
+    a.ax_nvalid = ax->n_valid; a.ax_out = ax->out;
+    if (p.pm == 2) hipLaunchKernelGGL((gemm_f32_mfma_xf<true, 2>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((gemm_f32_mfma_xf<true, 4>), grid, dim3(256), 0, st, a);
+    MVK_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
+  bool ok;
+  if (!transA && !transB) ok = launch_cfg<false, false>(p, grid, st, a);
+  else if (!transA && transB) ok = launch_cfg<false, true>(p, grid, st, a);
+  else if (transA && !transB) ok = launch_cfg<true, false>(p, grid, st, a);
+  else ok = launch_cfg<true, true>(p, grid, st, a);
+  MVK_REQUIRE(ok, "gemm: no kernel for plan pm=%d qn=%d narrow=%d", p.pm, p.qn, p.narrow);
+  MVK_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// two products that share A in one launch: behind mvk_gemm_f32_pair and mvk_gemm_f32_pair_bn
+int gemm_pair_run(const float* A, const float* B0, const float* B1, float* C0, float* C1, int64_t M, int64_t N0, int64_t N1,
+                  int64_t Kd, int transB, int want_stats, float* bn_part0, float* bn_part1, const int32_t* n_valid,
+                  const mvk_bn_finish* fin0, const mvk_bn_finish* fin1, void* stream) {
+  MVK_REQUIRE(M > 0 && N0 > 0 && N1 > 0 && Kd > 0, "gemm pair: empty product");
+  Plan p0 = plan_gemm(M, N0, Kd, 0, want_stats != 0), p1 = plan_gemm(M, N1, Kd, 0, want_stats != 0);
+  pair_widen(p0, p1, Kd);
+  MVK_REQUIRE(!p0.narrow && !p1.narrow && p0.pm == p1.pm && p0.qn == 1 && p1.qn == 1 && (p0.pm == 2 || p0.pm == 4),
+              "gemm pair: the two products do not share a tile shape (ask mvk_gemm_f32_pair_plan first)");
+  hipStream_t st = (hipStream_t)stream;
+  const bool ord = ordered_splits();
+  const KSplit s0 = clamp_split(Kd, p0.split), s1 = clamp_split(Kd, p1.split);
+  GemmArgs a0 = make_args(A, B0, C0, M, N0, Kd, Kd, transB ? Kd : N0, s0);
+  GemmArgs a1 = make_args(A, B1, C1, M, N1, Kd, Kd, transB ? Kd : N1, s1);
+  a0.bn_part = (want_stats && (p0.split == 1 || ord)) ? bn_part0 : nullptr;
+  a1.bn_part = (want_stats && (p1.split == 1 || ord)) ? bn_part1 : nullptr;
+  a0.n_valid = a1.n_valid = n_valid;
+  const int64_t tm = p0.tm(), tn = p0.tn(), gy = cdiv64(M, tm);
+  MVK_REQUIRE(gy < 65536 && s0.n < 65536 && s1.n < 65536, "gemm: grid too large");
+  const int gx0 = (int)cdiv64(N0, tn), gx1 = (int)cdiv64(N1, tn);
+  MVK_ORDERED(make_ordered(st, a0, s0.n, gx0, gy, tm, tn));
+  MVK_ORDERED(make_ordered(st, a1, s1.n, gx1, gy, tm, tn));
+  MVK_REQUIRE(ord || ((s0.n == 1 || !a0.bn_part) && (s1.n == 1 || !a1.bn_part)), "gemm pair: statistics of a split product");
+  if (int e = set_finish(a0, fin0, gy)) return e;
+  if (int e = set_finish(a1, fin1, gy)) return e;
+  dim3 grid((unsigned)(gx0 + gx1), (unsigned)gy, (unsigned)(s0.n > s1.n ? s0.n : s1.n));
+  const bool ok = transB ? launch_pair_cfg<false, true>(p0, grid, st, a0, a1, gx0, s0.n, s1.n)
+                         : launch_pair_cfg<false, false>(p0, grid, st, a0, a1, gx0, s0.n, s1.n);
+  MVK_REQUIRE(ok, "gemm pair: no kernel for plan pm=%d", p0.pm);
+  MVK_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
 }  // namespace
@@ -1045,11 +1145,7 @@ extern "C" int mvk_gemm_f32_dual_plan(int64_t M, int64_t N, int64_t Kd, int64_t 
   if (M == 0 || N == 0 || Kd == 0 || Kd2 == 0 || Kd % BK != 0) return 0;
   const Plan p = plan_gemm(M, N, Kd + Kd2, 0, false);
   if (p.narrow || p.qn != 1 || p.pm != 2) return 0;
-  int split = p.split;
-  const int64_t ksteps = cdiv64(Kd + Kd2, BK);
-  if (split > ksteps) split = (int)ksteps;
-  const int64_t k_per_split = cdiv64(ksteps, split) * BK;
-  *out_split = (int)cdiv64(Kd + Kd2, k_per_split);
+  *out_split = clamp_split(Kd + Kd2, p.split).n;
   return 0;
 }
 
@@ -1061,17 +1157,14 @@ extern "C" int mvk_gemm_f32_dual(const float* A, const float* B, const float* A2
   const Plan p = plan_gemm(M, N, Kd + Kd2, 0, false);
   MVK_REQUIRE(!p.narrow && p.qn == 1 && p.pm == 2, "gemm dual: unsupported shape (ask mvk_gemm_f32_dual_plan)");
   hipStream_t st = (hipStream_t)stream;
-  GemmArgs a;
-  const int split = fill_args(a, p, A, B, C, M, N, Kd + Kd2, 0, 0, nullptr, nullptr);
-  a.Kd = Kd;
-  a.lda = Kd;
-  a.vecA = ((a.lda % 4 == 0) && ((uintptr_t)A % 16 == 0)) ? 4 : ((a.lda % 2 == 0) && ((uintptr_t)A % 8 == 0)) ? 2 : 1;
+  const KSplit ks = clamp_split(Kd + Kd2, p.split);       // the split is planned on the whole reduction, as the plan export says
+  GemmArgs a = make_args(A, B, C, M, N, Kd, Kd, N, ks);
   a.A2 = A2; a.B2 = B2; a.Kd2 = Kd2; a.lda2 = Kd2; a.ldb2 = N;
-  a.vecA2 = ((a.lda2 % 4 == 0) && ((uintptr_t)A2 % 16 == 0)) ? 4 : ((a.lda2 % 2 == 0) && ((uintptr_t)A2 % 8 == 0)) ? 2 : 1;
-  a.vecB2 = ((a.ldb2 % 4 == 0) && ((uintptr_t)B2 % 16 == 0)) ? 4 : ((a.ldb2 % 2 == 0) && ((uintptr_t)B2 % 8 == 0)) ? 2 : 1;
-  MVK_REQUIRE(cdiv64(M, 32) < 65536 && split < 65536, "gemm: grid too large");
-  dim3 grid((unsigned)cdiv64(N, 64), (unsigned)cdiv64(M, 32), (unsigned)split);
-  MVK_ORDERED(make_ordered(st, a, split, (int)grid.x, grid.y, 32, 64));
+  a.vecA2 = vec_width(A2, a.lda2);
+  a.vecB2 = vec_width(B2, a.ldb2);
+  MVK_REQUIRE(cdiv64(M, 32) < 65536 && ks.n < 65536, "gemm: grid too large");
+  dim3 grid((unsigned)cdiv64(N, 64), (unsigned)cdiv64(M, 32), (unsigned)ks.n);
+  MVK_ORDERED(make_ordered(st, a, ks.n, (int)grid.x, grid.y, 32, 64));
   hipLaunchKernelGGL((gemm_f32_mfma_dual<false, false, 2, 1, 1, 4>), grid, dim3(256), 0, st, a);
   MVK_CHECK_HIP(hipGetLastError());
   return 0;
@@ -1090,19 +1183,14 @@ extern "C" int mvk_gemm_f32_pair_plan(int64_t M, int64_t N0, int64_t N1, int64_t
   out[0] = 1;
   out[1] = p0.split;
   out[2] = p1.split;
-  out[3] = (want_stats && (p0.split == 1 || ordered_splits())) ? 16 * p0.pm : 0;
-  out[4] = (want_stats && (p1.split == 1 || ordered_splits())) ? 16 * p1.pm : 0;
+  out[3] = (want_stats && (p0.split == 1 || ordered_splits())) ? (int)p0.tm() : 0;
+  out[4] = (want_stats && (p1.split == 1 || ordered_splits())) ? (int)p1.tm() : 0;
   return 0;
 }
 
 // C0 [M,N0] = A . op(B0) and C1 [M,N1] = A . op(B1) in ONE launch (A [M,Kd] row-major, not transposed; transB as in
 // mvk_gemm_f32_ex); plain stores (split reductions: atomics into zero-initialised outputs), statistics partials as in
 // mvk_gemm_f32_ex where the plan gives a row-block size. Fails when mvk_gemm_f32_pair_plan does not allow the pair.
-namespace {
-int gemm_pair_run(const float* A, const float* B0, const float* B1, float* C0, float* C1, int64_t M, int64_t N0, int64_t N1,
-                  int64_t Kd, int transB, int want_stats, float* bn_part0, float* bn_part1, const int32_t* n_valid,
-                  const mvk_bn_finish* fin0, const mvk_bn_finish* fin1, void* stream);
-}
 extern "C" int mvk_gemm_f32_pair(const float* A, const float* B0, const float* B1, float* C0, float* C1, int64_t M,
                                  int64_t N0, int64_t N1, int64_t Kd, int transB, int want_stats, float* bn_part0,
                                  float* bn_part1, const int32_t* n_valid, void* stream) {
@@ -1114,36 +1202,6 @@ extern "C" int mvk_gemm_f32_pair_bn(const float* A, const float* B0, const float
                                     const int32_t* n_valid, const mvk_bn_finish* fin0, const mvk_bn_finish* fin1, void* stream) {
   return gemm_pair_run(A, B0, B1, C0, C1, M, N0, N1, Kd, transB, 1, bn_part0, bn_part1, n_valid, fin0, fin1, stream);
 }
-namespace {
-int gemm_pair_run(const float* A, const float* B0, const float* B1, float* C0, float* C1, int64_t M, int64_t N0, int64_t N1,
-                  int64_t Kd, int transB, int want_stats, float* bn_part0, float* bn_part1, const int32_t* n_valid,
-                  const mvk_bn_finish* fin0, const mvk_bn_finish* fin1, void* stream) {
-  MVK_REQUIRE(M > 0 && N0 > 0 && N1 > 0 && Kd > 0, "gemm pair: empty product");
-  Plan p0 = plan_gemm(M, N0, Kd, 0, want_stats != 0), p1 = plan_gemm(M, N1, Kd, 0, want_stats != 0);
-  pair_widen(p0, p1, Kd);
-  MVK_REQUIRE(!p0.narrow && !p1.narrow && p0.pm == p1.pm && p0.qn == 1 && p1.qn == 1 && (p0.pm == 2 || p0.pm == 4),
-              "gemm pair: the two products do not share a tile shape (ask mvk_gemm_f32_pair_plan first)");
-  hipStream_t st = (hipStream_t)stream;
-  GemmArgs a0, a1;
-  const bool ord = ordered_splits();
-  const int s0 = fill_args(a0, p0, A, B0, C0, M, N0, Kd, 0, transB, (want_stats && (p0.split == 1 || ord)) ? bn_part0 : nullptr, n_valid);
-  const int s1 = fill_args(a1, p1, A, B1, C1, M, N1, Kd, 0, transB, (want_stats && (p1.split == 1 || ord)) ? bn_part1 : nullptr, n_valid);
-  const int64_t tm = 16 * p0.pm, tn = 64;
-  MVK_REQUIRE(cdiv64(M, tm) < 65536 && s0 < 65536 && s1 < 65536, "gemm: grid too large");
-  const int gx0 = (int)cdiv64(N0, tn), gx1 = (int)cdiv64(N1, tn);
-  MVK_ORDERED(make_ordered(st, a0, s0, gx0, cdiv64(M, tm), tm, tn));
-  MVK_ORDERED(make_ordered(st, a1, s1, gx1, cdiv64(M, tm), tm, tn));
-  MVK_REQUIRE(ord || ((s0 == 1 || !a0.bn_part) && (s1 == 1 || !a1.bn_part)), "gemm pair: statistics of a split product");
-  if (int e = set_finish(a0, fin0, cdiv64(M, tm))) return e;
-  if (int e = set_finish(a1, fin1, cdiv64(M, tm))) return e;
-  dim3 grid((unsigned)(gx0 + gx1), (unsigned)cdiv64(M, tm), (unsigned)(s0 > s1 ? s0 : s1));
-  const bool ok = transB ? launch_pair_cfg<false, true>(p0, grid, st, a0, a1, gx0, s0, s1)
-                         : launch_pair_cfg<false, false>(p0, grid, st, a0, a1, gx0, s0, s1);
-  MVK_REQUIRE(ok, "gemm pair: no kernel for plan pm=%d", p0.pm);
-  MVK_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-}  // namespace
 
 // Plan of mvk_gemm_f32_ex for a shape: the split of the reduction it will use (the caller zeroes C when > 1)
 // and the row-block size of the BatchNorm partials (0: no statistics are produced for this shape).
@@ -1157,28 +1215,15 @@ extern "C" int mvk_gemm_f32_plan(int64_t M, int64_t N, int64_t Kd, int split_k, 
   }
   const Plan p = plan_gemm(M, N, Kd, split_k > 0 ? split_k : 0, want_stats != 0);
   *out_split = p.split;
-  *out_stat_rows = (want_stats && (p.split == 1 || ordered_splits())) ? (p.narrow ? 64 * p.pm : 16 * p.pm) : 0;
+  *out_stat_rows = (want_stats && (p.split == 1 || ordered_splits())) ? (int)p.tm() : 0;
   return 0;
-}
-
-namespace {
-struct ScatterOut {
-  const void* idx;
-  int idx64, c1;
-  int64_t stride, ns;
-  float* dst;
-  float* rest;
-};
-int gemm_run(const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t Kd, int transA, int transB,
-             int accumulate, int split_k, float* bn_part, const int32_t* n_valid, const float* bias, float act_slope,
-             void* stream, const ScatterOut* scatter = nullptr, int seg_shift = -1, int64_t seg_extra = 0, int64_t ldb = 0,
-             const mvk_bn_finish* fin = nullptr, const mvk_a_transform* ax = nullptr);
 }
 
 extern "C" int mvk_gemm_f32_ex(const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t Kd,
                                int transA, int transB, int accumulate, int split_k, float* bn_part,
                                const int32_t* n_valid, void* stream) {
-  return gemm_run(A, B, C, M, N, Kd, transA, transB, accumulate, split_k, bn_part, n_valid, nullptr, 1.f, stream);
+  GemmOpts o; o.accumulate = accumulate; o.split_k = split_k; o.bn_part = bn_part; o.n_valid = n_valid;
+  return gemm_run(A, B, C, M, N, Kd, transA, transB, o, stream);
 }
 
 // mvk_gemm_f32_ex (A not transposed, plain store) with the BatchNorm on either side of the product folded into it
@@ -1188,7 +1233,8 @@ extern "C" int mvk_gemm_f32_bn(const float* A, const float* B, float* C, int64_t
                                float* bn_part, const int32_t* n_valid, const mvk_bn_finish* fin, const mvk_a_transform* ax,
                                void* stream) {
   MVK_REQUIRE(M > 0 && N > 0 && Kd > 0, "gemm bn: empty product");
-  return gemm_run(A, B, C, M, N, Kd, 0, transB, 0, 0, bn_part, n_valid, nullptr, 1.f, stream, nullptr, -1, 0, 0, fin, ax);
+  GemmOpts o; o.bn_part = bn_part; o.n_valid = n_valid; o.fin = fin; o.ax = ax;
+  return gemm_run(A, B, C, M, N, Kd, 0, transB, o, stream);
 }
 
 // C = LeakyReLU_slope(A . op(B) + bias[col]) (slope 1: the bias alone): a BatchNorm-less layer (blocks.py:462-463, the two
@@ -1196,7 +1242,8 @@ extern "C" int mvk_gemm_f32_bn(const float* A, const float* B, float* C, int64_t
 extern "C" int mvk_gemm_f32_bias_act(const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t Kd, int transB,
                                      const float* bias, float slope, void* stream) {
   MVK_REQUIRE(bias != nullptr && slope > 0.f && Kd > 0, "gemm bias_act: bias, a positive slope and a non-empty product");
-  return gemm_run(A, B, C, M, N, Kd, 0, transB, 0, 1, nullptr, nullptr, bias, slope, stream);
+  GemmOpts o; o.split_k = 1; o.bias = bias; o.act_slope = slope;
+  return gemm_run(A, B, C, M, N, Kd, 0, transB, o, stream);
 }
 
 // dx [M, Cin] = sum_k A[:, k, :] [M, Cout] . W[k]^T [Cout, Cin] with A [M, K, Cout] row-major and W [K, Cin, Cout] the
@@ -1207,15 +1254,16 @@ extern "C" int mvk_gemm_f32_kp_transposed(const float* A, const float* W, float*
   MVK_REQUIRE(K >= 1 && Cin >= 1 && Cout >= BK && (Cout & (Cout - 1)) == 0, "gemm kp_transposed: Cout must be a power of two >= 32");
   int shift = 0;
   while ((1 << shift) < Cout) ++shift;
-  return gemm_run(A, W, dx, M, Cin, (int64_t)K * Cout, 0, 1, 0, 0, nullptr, nullptr, nullptr, 1.f, stream, nullptr, shift,
-                  (int64_t)Cin * Cout - Cout);
+  GemmOpts o; o.seg_shift = shift; o.seg_extra = (int64_t)Cin * Cout - Cout;
+  return gemm_run(A, W, dx, M, Cin, (int64_t)K * Cout, 0, 1, o, stream);
 }
 
 // C [M,N] = A [M,Kd] . B with B [Kd, N] a column block of a wider row-major matrix (rows ldb >= N floats apart)
 extern "C" int mvk_gemm_f32_ldb(const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t Kd, int64_t ldb,
                                 void* stream) {
   MVK_REQUIRE(ldb >= N, "gemm ldb: ldb < N");
-  return gemm_run(A, B, C, M, N, Kd, 0, 0, 0, 0, nullptr, nullptr, nullptr, 1.f, stream, nullptr, -1, 0, ldb);
+  GemmOpts o; o.ldb = ldb;
+  return gemm_run(A, B, C, M, N, Kd, 0, 0, o, stream);
 }
 
 // [d_x | d_skip] = A [M,Kd] . B [Kd,N] where the product is the gradient of cat([x[idx[m,0]], skip[m]]) (decoder:
@@ -1227,87 +1275,9 @@ extern "C" int mvk_gemm_f32_scatter_cat(const float* A, const float* B, int64_t 
                                         void* stream) {
   MVK_REQUIRE(idx && d_x && d_skip && c1 > 0 && c1 < N && Kd > 0 && Ns >= 0 && idx_stride >= 1, "gemm scatter_cat: bad arguments");
   const ScatterOut sc{idx, idx64, c1, idx_stride, Ns, d_x, d_skip};
-  return gemm_run(A, B, d_skip /* unused */, M, N, Kd, 0, 0, 0, 0, nullptr, nullptr, nullptr, 1.f, stream, &sc);
+  GemmOpts o; o.scatter = &sc;
+  return gemm_run(A, B, d_skip /* unused */, M, N, Kd, 0, 0, o, stream);
 }
-
-namespace {
-int gemm_run(const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t Kd, int transA, int transB,
-             int accumulate, int split_k, float* bn_part, const int32_t* n_valid, const float* bias, float act_slope,
-             void* stream, const ScatterOut* scatter, int seg_shift, int64_t seg_extra, int64_t ldb,
-             const mvk_bn_finish* fin, const mvk_a_transform* ax) {
-  MVK_REQUIRE(M >= 0 && N >= 0 && Kd >= 0, "gemm: negative size");
-  if (M == 0 || N == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  MVK_REQUIRE(!(bn_part && (accumulate || Kd == 0)), "gemm: BatchNorm statistics need a plain store of a non-empty product");
-  if (Kd == 0) {
-    if (!accumulate && split_k <= 1) MVK_CHECK_HIP(hipMemsetAsync(C, 0, sizeof(float) * M * N, st));
-    return 0;
-  }
-  MVK_REQUIRE(!(bn_part && split_k > 1 && !ordered_splits()), "gemm: BatchNorm statistics need an unsplit (or ordered) reduction");
-  Plan p = plan_gemm(M, N, Kd, (bn_part && !ordered_splits()) ? 1 : (split_k > 0 ? split_k : 0), bn_part != nullptr);
-  int split = p.split;
-  const int64_t ksteps = cdiv64(Kd, BK);
-  if (split > ksteps) split = (int)ksteps;
-  const int64_t k_per_split = cdiv64(ksteps, split) * BK;
-  split = (int)cdiv64(Kd, k_per_split);
-  GemmArgs a;
-  a.A = A; a.B = B; a.C = C; a.M = M; a.N = N; a.Kd = Kd;
-  a.lda = transA ? M : Kd;
-  a.ldb = transB ? Kd : N;
-  a.k_per_split = k_per_split;
-  a.atomic_out = split > 1;
-  a.accumulate = accumulate;
-  a.vecA = ((a.lda % 4 == 0) && ((uintptr_t)A % 16 == 0)) ? 4 : ((a.lda % 2 == 0) && ((uintptr_t)A % 8 == 0)) ? 2 : 1;
-  a.vecB = ((a.ldb % 4 == 0) && ((uintptr_t)B % 16 == 0)) ? 4 : ((a.ldb % 2 == 0) && ((uintptr_t)B % 8 == 0)) ? 2 : 1;
-  if (ldb > 0) {                              // B = a column block of a wider matrix
-    a.ldb = ldb;
-    a.vecB = ((a.ldb % 4 == 0) && ((uintptr_t)B % 16 == 0)) ? 4 : ((a.ldb % 2 == 0) && ((uintptr_t)B % 8 == 0)) ? 2 : 1;
-  }
-  if (seg_shift >= 0) {
-    a.ldb = (int64_t)1 << seg_shift;          // rows of W[k]: Cout floats
-    a.vecB = ((uintptr_t)B % 16 == 0 && seg_extra % 4 == 0) ? 4 : 1;
-  }
-  a.bn_part = bn_part;
-  a.n_valid = n_valid;
-  a.bias = bias;
-  a.act_slope = act_slope;
-  a.A2 = nullptr; a.B2 = nullptr; a.Kd2 = 0; a.lda2 = 0; a.ldb2 = 0; a.vecA2 = 1; a.vecB2 = 1;
-  a.sc_idx = nullptr; a.sc_idx64 = 0; a.sc_c1 = 0; a.sc_stride = 0; a.sc_ns = 0; a.sc_dst = nullptr; a.sc_rest = nullptr;
-  a.seg_shift = seg_shift;
-  a.seg_extra = seg_extra;
-  no_bn_fold(a);
-  if (scatter) {
-    a.sc_idx = scatter->idx; a.sc_idx64 = scatter->idx64; a.sc_c1 = scatter->c1; a.sc_stride = scatter->stride;
-    a.sc_ns = scatter->ns; a.sc_dst = scatter->dst; a.sc_rest = scatter->rest;
-  }
-  const int64_t tm = p.narrow ? 64 * p.pm : 16 * p.pm, tn = p.narrow ? 16 * p.qn : 64 * p.qn;
-  MVK_REQUIRE(cdiv64(M, tm) < 65536 && split < 65536, "gemm: grid too large");
-  dim3 grid((unsigned)cdiv64(N, tn), (unsigned)cdiv64(M, tm), (unsigned)split);
-  MVK_ORDERED(make_ordered(st, a, split, (int)grid.x, grid.y, tm, tn));
-  MVK_REQUIRE(!(bn_part && split > 1 && !a.det_ws), "gemm: BatchNorm statistics of a split product need the ordered reduction");
-  if (int e = set_finish(a, fin, grid.y)) return e;
-  if (ax) {
-    // the consumer's half of a folded BatchNorm (GemmArgs (b)): wide NT tiles, the workgroup's k-range inside the table
-    MVK_REQUIRE(!transA && transB && !p.narrow && p.qn == 1 && (p.pm == 2 || p.pm == 4) && k_per_split <= XF_KMAX && !scatter &&
-                    seg_shift < 0 && ax->mean && ax->invstd && ax->gamma && ax->beta && ax->slope > 0.f,
-                "gemm: the operand transform needs an NT product of more than 32 columns with k-ranges <= %d", XF_KMAX);
-    a.ax_mean = ax->mean; a.ax_invstd = ax->invstd; a.ax_gamma = ax->gamma; a.ax_beta = ax->beta; a.ax_slope = ax->slope;
-    a.ax_nvalid = ax->n_valid; a.ax_out = ax->out;
-    if (p.pm == 2) hipLaunchKernelGGL((gemm_f32_mfma_xf<true, 2>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((gemm_f32_mfma_xf<true, 4>), grid, dim3(256), 0, st, a);
-    MVK_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-  bool ok;
-  if (!transA && !transB) ok = launch_cfg<false, false>(p, grid, st, a);
-  else if (!transA && transB) ok = launch_cfg<false, true>(p, grid, st, a);
-  else if (transA && !transB) ok = launch_cfg<true, false>(p, grid, st, a);
-  else ok = launch_cfg<true, true>(p, grid, st, a);
-  MVK_REQUIRE(ok, "gemm: no kernel for plan pm=%d qn=%d narrow=%d", p.pm, p.qn, p.narrow);
-  MVK_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-}  // namespace
 
 // One record of mvk_gemm_f32_tn_grouped (host side, 48 bytes): C [M,N] (+)= A^T B with A [Kd,M], B [Kd,N] row-major.
 struct MvkGemmProblem {
@@ -1378,29 +1348,10 @@ extern "C" int mvk_gemm_f32_tn_grouped_plan(const void* problems, int n, void* t
     MVK_REQUIRE(q.M > 0 && q.N > 0 && q.Kd > 0 && q.A && q.B && q.C, "grouped gemm: empty problem %d", i);
     const bool narrow = q.N <= 32;
     MVK_REQUIRE(!narrow || q.N > 16, "grouped gemm: outputs of <= 16 columns are not grouped");
-    int split = grouped_split_at(q.M, q.N, q.Kd, ktiles);
-    const int64_t ksteps = cdiv64(q.Kd, BK);
-    if (split > ksteps) split = (int)ksteps;
-    const int64_t k_per_split = cdiv64(ksteps, split) * BK;
-    split = (int)cdiv64(q.Kd, k_per_split);
-    GroupEntry e;
-    e.args.A = q.A; e.args.B = q.B; e.args.C = q.C; e.args.M = q.M; e.args.N = q.N; e.args.Kd = q.Kd;
-    e.args.lda = q.M; e.args.ldb = q.N;      // TN: A [Kd,M], B [Kd,N]
-    e.args.k_per_split = k_per_split;
-    e.args.atomic_out = split > 1;
-    e.args.accumulate = 0;
-    e.args.vecA = ((q.M % 4 == 0) && ((uintptr_t)q.A % 16 == 0)) ? 4 : ((q.M % 2 == 0) && ((uintptr_t)q.A % 8 == 0)) ? 2 : 1;
-    e.args.vecB = ((q.N % 4 == 0) && ((uintptr_t)q.B % 16 == 0)) ? 4 : ((q.N % 2 == 0) && ((uintptr_t)q.B % 8 == 0)) ? 2 : 1;
-    e.args.bn_part = nullptr;
-    e.args.n_valid = nullptr;
-    e.args.bias = nullptr;
-    e.args.act_slope = 1.f;
-    e.args.A2 = nullptr; e.args.B2 = nullptr; e.args.Kd2 = 0; e.args.lda2 = 0; e.args.ldb2 = 0;
-    e.args.vecA2 = 1; e.args.vecB2 = 1;
-    e.args.sc_idx = nullptr; e.args.sc_idx64 = 0; e.args.sc_c1 = 0; e.args.sc_stride = 0; e.args.sc_ns = 0;
-    e.args.sc_dst = nullptr; e.args.sc_rest = nullptr;
-    e.args.seg_shift = -1; e.args.seg_extra = 0;
-    no_bn_fold(e.args);
+    const KSplit ks = clamp_split(q.Kd, grouped_split_at(q.M, q.N, q.Kd, ktiles));
+    const int split = ks.n;
+    GroupEntry e{};
+    e.args = make_args(q.A, q.B, q.C, q.M, q.N, q.Kd, q.M, q.N, ks);      // TN: A [Kd,M], B [Kd,N]
     const int64_t tm = narrow ? 64 : 16 * group_wide_pm(), tn = narrow ? 32 : 64;      // plan tiles: narrow (pm 1, qn 2), wide (pm 2, qn 1)
     e.gx = (int)cdiv64(q.N, tn);
     e.gy = (int)cdiv64(q.M, tm);
