@@ -28,6 +28,21 @@ extern "C" void mvk_set_error(const char* fmt, ...);
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Hands out consecutive 16-byte aligned slices of a workspace of `bytes` bytes. take() never fails: a function carves
+// all of its fields and then checks fits() once, before anything touches them.
+struct Carver {
+  char* p;
+  char* end;
+  Carver(void* ws, int64_t bytes) : p((char*)ws), end((char*)ws + bytes) {}
+  template <typename T>
+  T* take(int64_t count) {
+    uintptr_t a = ((uintptr_t)p + 15) & ~(uintptr_t)15;
+    p = (char*)a + sizeof(T) * count;
+    return (T*)a;
+  }
+  bool fits() const { return p <= end; }
+};
+
 // Slices of the arena of ordered reductions (mvk_gemm_split_arena, csrc/gemm.hip) for kernels outside the GEMM that sum
 // per-workgroup partials in a fixed order: `floats` of parking space, `counters` zeroed int32 words that the kernel must
 // leave at zero, for a launch on `stream` (a capturing stream keeps its slices for good, gemm.hip). False: no arena is

@@ -609,20 +609,33 @@ __global__ __launch_bounds__(64 * WV) void nb_query_wide_kernel(const float* __r
   for (int c = n + tid; c < width; c += T) out[i * width + c] = (int)Ns;
 }
 
-struct Carver {
-  char* p;
-  template <typename T>
-  T* take(int64_t count) {
-    uintptr_t a = ((uintptr_t)p + 15) & ~(uintptr_t)15;
-    p = (char*)a + sizeof(T) * count;
-    return (T*)a;
-  }
-};
-
 int64_t ws_bytes(int64_t Nq, int64_t Ns, int B) {
   int64_t cells = cell_cap(Ns) + (int64_t)B * (4096 + 1 + 4);
   return (int64_t)B * sizeof(CloudGrid) + 2 * cells * 4 + (Ns + 1) * 16 + 2 * (int64_t)(B + 1) * 4 +
          (Nq + 1) * 4 + 64 + 16 * 12 + 16;
+}
+
+// The one layout of a neighbour workspace. The grid part comes first and depends on (Ns, B) only: a search that reuses
+// the grid of the call before it (reuse_grid) and mvk_neighbors_cell_order (Nq = 0) read what a call with another Nq
+// carved. hdr = {max count, overflow, 2 spare words, query offsets [B + 1], support offsets [B + 1]}; the two counters
+// default to hdr[0] / hdr[1]. False (error set): the fields do not fit into `bytes`.
+bool carve(void* ws, int64_t bytes, int64_t Nq, int64_t Ns, int B, NbWs& W, int** hdr_out = nullptr) {
+  Carver cv(ws, bytes);
+  const int64_t cells = cell_cap(Ns) + (int64_t)B * (4096 + 1 + 4);
+  W = NbWs{};
+  W.grids = cv.take<CloudGrid>(B);
+  W.cell_start = cv.take<int>(cells);
+  W.cell_fill = cv.take<int>(cells);
+  W.recs = cv.take<float4>(Ns + 1);
+  int* hdr = cv.take<int>(4 + 2 * (B + 1));
+  if (hdr_out) *hdr_out = hdr;
+  W.maxcount = hdr;
+  W.overflow = hdr + 1;
+  W.qoffs = hdr + 4;
+  W.soffs = hdr + 4 + B + 1;
+  W.counts = cv.take<int>(Nq + 1);
+  if (!cv.fits()) mvk_set_error("neighbors: workspace carve overflow");
+  return cv.fits();
 }
 
 }  // namespace
@@ -663,6 +676,23 @@ void launch_build(const float* s, const NbWs& W, float radius, int B, int64_t ma
   hipLaunchKernelGGL(nb_scatter_kernel, g, dim3(256), 0, st, s, W);
 }
 
+// The one rule that picks the kernel writing `rows` rows of `width` columns (`shadow` fills the tails). Narrow rows
+// of an enqueue-only search (status word: nobody reads the counters back before the next launch) keep a 256-entry
+// list -- a row holding more than 4x the calibrated limit is reported through the overflow flag like a row beyond
+// LIST_CAP -- and can fill the transposed relation `rev` on the way; wider rows take eight wavefronts per query.
+void launch_query(const float* q, const NbWs& W, int B, float radius, int64_t shadow, int64_t rows, int32_t* out,
+                  int width, bool status_word, const RevOut* rev, hipStream_t st) {
+  const dim3 g((unsigned)rows);
+  if (width <= 64 && status_word && rev)
+    hipLaunchKernelGGL((nb_query_kernel<true, 256, true>), g, dim3(64), 0, st, q, W, B, radius, shadow, out, width, *rev);
+  else if (width <= 64 && status_word)
+    hipLaunchKernelGGL((nb_query_kernel<true, 256>), g, dim3(64), 0, st, q, W, B, radius, shadow, out, width, RevOut{});
+  else if (width > 64 && wide_waves() > 1)
+    hipLaunchKernelGGL((nb_query_wide_kernel<8>), g, dim3(512), 0, st, q, W, B, radius, shadow, out, width);
+  else
+    hipLaunchKernelGGL((nb_query_kernel<true, LIST_CAP>), g, dim3(64), 0, st, q, W, B, radius, shadow, out, width, RevOut{});
+}
+
 // Common body. status_dev == nullptr: classic two-phase contract (synchronises, reports through
 // width_host). status_dev != nullptr: enqueue only -- the max row count / overflow flag are folded into
 // status_dev[0] / status_dev[1] on the device. reuse_grid: the workspace still holds the grid built by
@@ -693,20 +723,9 @@ int nb_run(const float* q, int64_t Nq, const float* s, int64_t Ns, const int32_t
   hdr_h[0] = hdr_h[1] = hdr_h[2] = hdr_h[3] = 0;
   MVK_REQUIRE(tq == Nq && ts == Ns, "neighbors: batch lengths do not sum to the point counts");
 
-  Carver cv{(char*)workspace};
-  NbWs W{};
-  int64_t cells = cell_cap(Ns) + (int64_t)B * (4096 + 1 + 4);
-  W.grids = cv.take<CloudGrid>(B);              // grid part first: its layout depends on (Ns, B) only
-  W.cell_start = cv.take<int>(cells);
-  W.cell_fill = cv.take<int>(cells);
-  W.recs = cv.take<float4>(Ns + 1);
-  int* hdr = cv.take<int>(4 + 2 * (B + 1));
-  W.maxcount = hdr;
-  W.overflow = hdr + 1;
-  W.qoffs = hdr + 4;
-  W.soffs = hdr + 4 + B + 1;
-  W.counts = cv.take<int>(Nq + 1);
-  MVK_REQUIRE(cv.p <= (char*)workspace + workspace_bytes, "neighbors: workspace carve overflow");
+  NbWs W;
+  int* hdr;
+  if (!carve(workspace, workspace_bytes, Nq, Ns, B, W, &hdr)) return -1;
   if (status_dev) {
     W.maxcount = status_dev;
     W.overflow = status_dev + 1;
@@ -729,16 +748,7 @@ int nb_run(const float* q, int64_t Nq, const float* s, int64_t Ns, const int32_t
     return 0;
   }
   MVK_REQUIRE(width >= 0, "neighbors: negative width");
-  if (Nq > 0 && width > 0) {
-    // enqueue-only mode with a column limit: a row holding more than 4x the calibrated limit is reported
-    // through the overflow flag like a row beyond LIST_CAP
-    if (status_dev && width <= 64)
-      hipLaunchKernelGGL((nb_query_kernel<true, 256>), dim3((unsigned)Nq), dim3(64), 0, st, q, W, B, radius, Ns, out, width, RevOut{});
-    else if (wide_waves() > 1 && width > 64)
-      hipLaunchKernelGGL((nb_query_wide_kernel<8>), dim3((unsigned)Nq), dim3(512), 0, st, q, W, B, radius, Ns, out, width);
-    else
-      hipLaunchKernelGGL((nb_query_kernel<true, LIST_CAP>), dim3((unsigned)Nq), dim3(64), 0, st, q, W, B, radius, Ns, out, width, RevOut{});
-  }
+  if (Nq > 0 && width > 0) launch_query(q, W, B, radius, Ns, Nq, out, width, status_dev != nullptr, nullptr, st);
   MVK_CHECK_HIP(hipGetLastError());
   if (status_dev) return 0;
   int res[2] = {0, 0};
@@ -771,10 +781,28 @@ extern "C" int mvk_radius_neighbors_enqueue(const float* q, int64_t Nq, const fl
 }
 
 namespace {
+// Device-lens body (capturable: no host reads, fixed launch geometry): the batch lengths stay on the device and the
+// counters are folded into status_dev. rev: also fill the transposed relation (mvk_radius_neighbors_dev_rev).
 int nb_dev_run(const float* q, int64_t Nq_cap, const float* s, int64_t Ns_cap, const int32_t* q_lens_dev,
                const int32_t* s_lens_dev, int B, float radius, int32_t* out, int width, int32_t shadow, int32_t* status_dev,
-               int reuse_grid, void* workspace, int64_t workspace_bytes, const RevOut* rev, void* stream);
+               int reuse_grid, void* workspace, int64_t workspace_bytes, const RevOut* rev, void* stream) {
+  MVK_REQUIRE(B >= 1 && B <= 4096 && Nq_cap >= 1 && Ns_cap >= 1 && Nq_cap < (1ll << 31) && Ns_cap < (1ll << 29),
+              "neighbors: bad sizes");
+  MVK_REQUIRE(radius > 0.f && width >= 1 && out && status_dev, "neighbors: bad arguments");
+  MVK_REQUIRE(workspace && workspace_bytes >= ws_bytes(Nq_cap, Ns_cap, B), "neighbors: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  NbWs W;
+  if (!carve(workspace, workspace_bytes, Nq_cap, Ns_cap, B, W)) return -1;
+  W.maxcount = status_dev;
+  W.overflow = status_dev + 1;
+  W.q_lens = q_lens_dev;       // the kernels derive the offsets themselves (was: a one-thread launch per search)
+  W.s_lens = s_lens_dev;
+  if (!reuse_grid) launch_build(s, W, radius, B, Ns_cap, st);
+  launch_query(q, W, B, radius, shadow, Nq_cap, out, width, true, rev, st);
+  MVK_CHECK_HIP(hipGetLastError());
+  return 0;
 }
+}  // namespace
 
 extern "C" int mvk_radius_neighbors_dev(const float* q, int64_t Nq_cap, const float* s, int64_t Ns_cap,
                                         const int32_t* q_lens_dev, const int32_t* s_lens_dev, int B,
@@ -802,49 +830,6 @@ extern "C" int mvk_radius_neighbors_dev_rev(const float* q, int64_t Nq_cap, cons
                     workspace, workspace_bytes, &R, stream);
 }
 
-namespace {
-int nb_dev_run(const float* q, int64_t Nq_cap, const float* s, int64_t Ns_cap, const int32_t* q_lens_dev,
-               const int32_t* s_lens_dev, int B, float radius, int32_t* out, int width, int32_t shadow, int32_t* status_dev,
-               int reuse_grid, void* workspace, int64_t workspace_bytes, const RevOut* rev, void* stream) {
-  MVK_REQUIRE(B >= 1 && B <= 4096 && Nq_cap >= 1 && Ns_cap >= 1 && Nq_cap < (1ll << 31) && Ns_cap < (1ll << 29),
-              "neighbors: bad sizes");
-  MVK_REQUIRE(radius > 0.f && width >= 1 && out && status_dev, "neighbors: bad arguments");
-  MVK_REQUIRE(workspace && workspace_bytes >= ws_bytes(Nq_cap, Ns_cap, B), "neighbors: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  Carver cv{(char*)workspace};
-  NbWs W{};
-  int64_t cells = cell_cap(Ns_cap) + (int64_t)B * (4096 + 1 + 4);
-  W.grids = cv.take<CloudGrid>(B);
-  W.cell_start = cv.take<int>(cells);
-  W.cell_fill = cv.take<int>(cells);
-  W.recs = cv.take<float4>(Ns_cap + 1);
-  int* hdr = cv.take<int>(4 + 2 * (B + 1));
-  W.qoffs = hdr + 4;
-  W.soffs = hdr + 4 + B + 1;
-  W.counts = cv.take<int>(Nq_cap + 1);
-  MVK_REQUIRE(cv.p <= (char*)workspace + workspace_bytes, "neighbors: workspace carve overflow");
-  W.maxcount = status_dev;
-  W.overflow = status_dev + 1;
-  W.q_lens = q_lens_dev;       // the kernels derive the offsets themselves (was: a one-thread launch per search)
-  W.s_lens = s_lens_dev;
-  if (!reuse_grid) launch_build(s, W, radius, B, Ns_cap, st);
-  if (width <= 64 && rev)
-    hipLaunchKernelGGL((nb_query_kernel<true, 256, true>), dim3((unsigned)Nq_cap), dim3(64), 0, st, q, W, B, radius,
-                       (int64_t)shadow, out, width, *rev);
-  else if (width <= 64)
-    hipLaunchKernelGGL((nb_query_kernel<true, 256>), dim3((unsigned)Nq_cap), dim3(64), 0, st, q, W, B, radius,
-                       (int64_t)shadow, out, width, RevOut{});
-  else if (wide_waves() > 1)
-    hipLaunchKernelGGL((nb_query_wide_kernel<8>), dim3((unsigned)Nq_cap), dim3(512), 0, st, q, W, B, radius,
-                       (int64_t)shadow, out, width);
-  else
-    hipLaunchKernelGGL((nb_query_kernel<true, LIST_CAP>), dim3((unsigned)Nq_cap), dim3(64), 0, st, q, W, B, radius,
-                       (int64_t)shadow, out, width, RevOut{});
-  MVK_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-}  // namespace
-
 // The supports of the grid the workspace holds (built by the last search on it: same Ns, B and lengths), as a work
 // list for mvk_kpconv_gather_fwd_ordered: order_out[0 .. total) = the stacked rows sorted by cloud, grid cell
 // (x fastest) and row; order_out[total .. order_cap) = identity. s_lens_dev: the device lengths of a
@@ -853,15 +838,8 @@ extern "C" int mvk_neighbors_cell_order(int64_t Ns, int B, const int32_t* s_lens
                                         int64_t order_cap, void* workspace, int64_t workspace_bytes, void* stream) {
   MVK_REQUIRE(B >= 1 && B <= 4096 && Ns >= 0 && Ns < (1ll << 29) && order_out && order_cap >= Ns, "cell order: bad arguments");
   MVK_REQUIRE(workspace && workspace_bytes >= ws_bytes(0, Ns, B), "cell order: workspace too small");
-  Carver cv{(char*)workspace};
-  NbWs W{};
-  int64_t cells = cell_cap(Ns) + (int64_t)B * (4096 + 1 + 4);
-  W.grids = cv.take<CloudGrid>(B);
-  W.cell_start = cv.take<int>(cells);
-  W.cell_fill = cv.take<int>(cells);
-  W.recs = cv.take<float4>(Ns + 1);
-  int* hdr = cv.take<int>(4 + 2 * (B + 1));
-  W.soffs = hdr + 4 + B + 1;
+  NbWs W;
+  if (!carve(workspace, workspace_bytes, 0, Ns, B, W)) return -1;      // the grid part does not depend on Nq
   W.s_lens = s_lens_dev;
   // a thread's cells are chains of dependent loads (cell range -> records -> stores): one workgroup per cloud took
   // 150 us on the level-0 grid of a 19 464-point sphere (15 cells per thread, one after the other)

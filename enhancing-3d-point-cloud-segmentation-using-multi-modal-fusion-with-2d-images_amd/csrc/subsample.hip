@@ -877,18 +877,6 @@ __global__ void subsample_finish_dev_kernel(SubWs W, int B, float* __restrict__ 
   }
 }
 
-struct Carver {
-  char* p;
-  char* end;
-  template <typename T>
-  T* take(int64_t count) {
-    uintptr_t a = ((uintptr_t)p + 15) & ~(uintptr_t)15;
-    T* r = (T*)a;
-    p = (char*)a + sizeof(T) * count;
-    return r;
-  }
-};
-
 int64_t ws_bytes(int64_t N, int B, int fdim, int ldim) {
   int64_t n = N > 0 ? N : 1;
   int64_t bytes = 0;
@@ -903,6 +891,42 @@ int64_t ws_bytes(int64_t N, int B, int fdim, int ldim) {
   bytes += n * 12 + 16;                     // rot_pts (oriented variant)
   bytes += (int64_t)B * (6 + 1) * 4 + ((n + 255) / 256 + 1) * (int64_t)B * 4 + 64;   // bbox, mdev, wgcnt (multi-workgroup front end)
   return bytes + 64 * 32;
+}
+
+// The one layout of a subsampling workspace for n >= 1 point rows (the device-lens entry has fdim = ldim = 0: its
+// feature / label fields keep one element each). Besides the fields of W: the host-length entry's cloud offsets
+// offs_d [B + 1] and the oriented copy of the points rot_pts [n, 3]. False (error set): it does not fit into `bytes`.
+bool carve(void* ws, int64_t bytes, int64_t n, int B, int fdim, int ldim, SubWs& W, int*& offs_d, float*& rot_pts) {
+  Carver cv(ws, bytes);
+  const int64_t nf = n * (fdim > 0 ? fdim : 0) + 1, nl = n * (ldim > 0 ? ldim : 0) + 1, nbk = 3 * n + 32 * B;
+  W = SubWs{};
+  W.slot = cv.take<int>(n); W.member = cv.take<int>(n); W.scan = cv.take<int>(n);
+  W.hkey = cv.take<unsigned long long>(4 * n); W.hfirst = cv.take<int>(4 * n); W.hvox = cv.take<int>(4 * n);
+  W.vkey = cv.take<unsigned long long>(n); W.vcount = cv.take<int>(n); W.vseg = cv.take<int>(n);
+  W.vcursor = cv.take<int>(n); W.vbary = cv.take<float>(3 * n);
+  W.vfeat = cv.take<float>(nf);
+  W.vlab = cv.take<int>(nl);
+  W.lab_key = cv.take<int>(n); W.lab_cnt = cv.take<int>(n); W.errflag = cv.take<int>(1);
+  W.tau = cv.take<int>(n); W.posnew = cv.take<int>(n); W.nextb = cv.take<int>(n); W.tarr = cv.take<int>(n);
+  W.ft = cv.take<int>(nbk); W.bcnt = cv.take<int>(nbk); W.bhead = cv.take<int>(nbk);
+  W.out_count = cv.take<int>(B + 1);
+  offs_d = cv.take<int>(B + 1);
+  W.stage_pts = cv.take<float>(3 * n);
+  W.stage_feat = cv.take<float>(nf);
+  W.stage_lab = cv.take<int>(nl);
+  rot_pts = cv.take<float>(3 * n);
+  W.bbox = cv.take<unsigned int>(6 * B); W.mdev = cv.take<int>(B); W.wgcnt = cv.take<int>(((n + 255) / 256 + 1) * B);
+  if (!cv.fits()) mvk_set_error("subsample: workspace carve overflow");
+  return cv.fits();
+}
+
+// _Prime_rehash_policy::_M_need_rehash: first allocation 13 buckets, then
+// next_bkt(max(count + 2, 2 * nb)) = next_bkt(2 * nb) each time count reaches nb.
+Schedule make_schedule() {
+  Schedule sched;
+  sched.nb[0] = 13;
+  for (int e = 1; e < 48; ++e) sched.nb[e] = mvk_next_bkt(2 * sched.nb[e - 1]);
+  return sched;
 }
 
 }  // namespace
@@ -996,41 +1020,28 @@ int subsample_run(const float* pts, int64_t N, const int32_t* lens_host, int B, 
   if (max_p < 1) max_p = (int)(N > 0 ? N : 1);  // grid_subsampling.cpp:134-135
 
   const int64_t n = N > 0 ? N : 1;
-  Carver cv{(char*)workspace, (char*)workspace + workspace_bytes};
-  SubWs W{};
-  W.slot = cv.take<int>(n); W.member = cv.take<int>(n); W.scan = cv.take<int>(n);
-  W.hkey = cv.take<unsigned long long>(4 * n); W.hfirst = cv.take<int>(4 * n); W.hvox = cv.take<int>(4 * n);
-  W.vkey = cv.take<unsigned long long>(n); W.vcount = cv.take<int>(n); W.vseg = cv.take<int>(n);
-  W.vcursor = cv.take<int>(n); W.vbary = cv.take<float>(3 * n);
-  W.vfeat = cv.take<float>(n * (fdim > 0 ? fdim : 0) + 1);
-  W.vlab = cv.take<int>(n * (ldim > 0 ? ldim : 0) + 1);
-  W.lab_key = cv.take<int>(n); W.lab_cnt = cv.take<int>(n); W.errflag = cv.take<int>(1);
-  W.tau = cv.take<int>(n); W.posnew = cv.take<int>(n); W.nextb = cv.take<int>(n); W.tarr = cv.take<int>(n);
-  W.ft = cv.take<int>(3 * n + 32 * B); W.bcnt = cv.take<int>(3 * n + 32 * B); W.bhead = cv.take<int>(3 * n + 32 * B);
-  W.out_count = cv.take<int>(B + 1);
-  int* offs_d = cv.take<int>(B + 1);
-  W.stage_pts = cv.take<float>(3 * n);
-  W.stage_feat = cv.take<float>(n * (fdim > 0 ? fdim : 0) + 1);
-  W.stage_lab = cv.take<int>(n * (ldim > 0 ? ldim : 0) + 1);
-  float* rot_pts = cv.take<float>(3 * n);
-  W.bbox = cv.take<unsigned int>(6 * B); W.mdev = cv.take<int>(B); W.wgcnt = cv.take<int>(((n + 255) / 256 + 1) * B);
-  MVK_REQUIRE(cv.p <= cv.end, "subsample: workspace carve overflow");
-  if (rot_host) {   // random grid orientation (datasets/common.py:89-118): rotate every cloud by its matrix
+  SubWs W;
+  int* offs_d;
+  float* rot_pts;
+  if (!carve(workspace, workspace_bytes, n, B, fdim, ldim, W, offs_d, rot_pts)) return -1;
+  // one launch per non-empty cloud, rotating it by its matrix; its rows are the input rows (offs_h / lens_host), or,
+  // with count_dev, the rows of the compacted output, whose counts only the device knows
+  auto rotate_clouds = [&](const float* in, float* out, const int32_t* count_dev, int transpose) {
     for (int b = 0; b < B; ++b) {
       if (lens_host[b] == 0) continue;
       Rot3 R;
       for (int i = 0; i < 9; ++i) R.m[i] = rot_host[b * 9 + i];
-      hipLaunchKernelGGL(rotate_cloud_kernel, dim3((unsigned)cdiv64(lens_host[b], 256)), dim3(256), 0, st, pts, rot_pts,
-                         (int64_t)offs_h[b], (int64_t)lens_host[b], (const int32_t*)nullptr, b, R, 0);
+      hipLaunchKernelGGL(rotate_cloud_kernel, dim3((unsigned)cdiv64(lens_host[b], 256)), dim3(256), 0, st, in, out,
+                         (int64_t)(count_dev ? 0 : offs_h[b]), (int64_t)(count_dev ? 0 : lens_host[b]), count_dev, b, R,
+                         transpose);
     }
+  };
+  if (rot_host) {   // random grid orientation (datasets/common.py:89-118): rotate every cloud by its matrix
+    rotate_clouds(pts, rot_pts, nullptr, 0);
     pts = rot_pts;
   }
 
-  // _Prime_rehash_policy::_M_need_rehash: first allocation 13 buckets, then
-  // next_bkt(max(count + 2, 2 * nb)) = next_bkt(2 * nb) each time count reaches nb.
-  Schedule sched;
-  sched.nb[0] = 13;
-  for (int e = 1; e < 48; ++e) sched.nb[e] = mvk_next_bkt(2 * sched.nb[e - 1]);
+  const Schedule sched = make_schedule();
   MVK_CHECK_HIP(hipMemcpyAsync(offs_d, offs_h, sizeof(int) * (B + 1), hipMemcpyHostToDevice, st));
   MVK_CHECK_HIP(hipMemsetAsync(W.errflag, 0, sizeof(int), st));
   static const bool timing = getenv("MVK_SUB_TIMING") != nullptr;
@@ -1060,15 +1071,8 @@ int subsample_run(const float* pts, int64_t N, const int32_t* lens_host, int B, 
   if (gx > 64) gx = 64;
   hipLaunchKernelGGL(subsample_compact_kernel, dim3(gx, B), dim3(256), 0, st, offs_d, W, B, fdim, ldim, max_p,
                      out_pts, out_feats, out_labels, out_lens, (int64_t)n, (int*)nullptr);
-  if (rot_host) {   // ... and the barycentres back by its transpose (:134), in place on the compacted output
-    for (int b = 0; b < B; ++b) {
-      if (lens_host[b] == 0) continue;
-      Rot3 R;
-      for (int i = 0; i < 9; ++i) R.m[i] = rot_host[b * 9 + i];
-      hipLaunchKernelGGL(rotate_cloud_kernel, dim3((unsigned)cdiv64(lens_host[b], 256)), dim3(256), 0, st, out_pts, out_pts,
-                         (int64_t)0, (int64_t)0, (const int32_t*)out_lens, b, R, 1);
-    }
-  }
+  // ... and the barycentres back by its transpose (:134), in place on the compacted output
+  if (rot_host) rotate_clouds(out_pts, out_pts, out_lens, 1);
   MVK_CHECK_HIP(hipGetLastError());
   if (out_lens_host)
     MVK_CHECK_HIP(hipMemcpyAsync(out_lens_host, out_lens, sizeof(int) * B, hipMemcpyDeviceToHost, st));
@@ -1111,31 +1115,13 @@ extern "C" int mvk_grid_subsample_batch_dev(const float* pts, int64_t cap_in, co
   MVK_REQUIRE(status_dev != nullptr && out_lens_dev != nullptr, "subsample: the device-lens variant needs a status word");
   MVK_REQUIRE(workspace != nullptr && workspace_bytes >= ws_bytes(cap_in, B, 0, 0), "subsample: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  const int64_t n = cap_in;
-  Carver cv{(char*)workspace, (char*)workspace + workspace_bytes};
-  SubWs W{};
-  W.slot = cv.take<int>(n); W.member = cv.take<int>(n); W.scan = cv.take<int>(n);
-  W.hkey = cv.take<unsigned long long>(4 * n); W.hfirst = cv.take<int>(4 * n); W.hvox = cv.take<int>(4 * n);
-  W.vkey = cv.take<unsigned long long>(n); W.vcount = cv.take<int>(n); W.vseg = cv.take<int>(n);
-  W.vcursor = cv.take<int>(n); W.vbary = cv.take<float>(3 * n);
-  W.vfeat = cv.take<float>(1);
-  W.vlab = cv.take<int>(1);
-  W.lab_key = cv.take<int>(n); W.lab_cnt = cv.take<int>(n); W.errflag = cv.take<int>(1);
-  W.tau = cv.take<int>(n); W.posnew = cv.take<int>(n); W.nextb = cv.take<int>(n); W.tarr = cv.take<int>(n);
-  W.ft = cv.take<int>(3 * n + 32 * B); W.bcnt = cv.take<int>(3 * n + 32 * B); W.bhead = cv.take<int>(3 * n + 32 * B);
-  W.out_count = cv.take<int>(B + 1);
-  cv.take<int>(B + 1);
-  W.stage_pts = cv.take<float>(3 * n);
-  W.stage_feat = cv.take<float>(1);
-  W.stage_lab = cv.take<int>(1);
-  float* rot_pts = cv.take<float>(3 * n);
-  W.bbox = cv.take<unsigned int>(6 * B); W.mdev = cv.take<int>(B); W.wgcnt = cv.take<int>(((n + 255) / 256 + 1) * B);
-  MVK_REQUIRE(cv.p <= cv.end, "subsample: workspace carve overflow");
+  SubWs W;
+  int* offs_d;       // unused here: the kernels derive the offsets from lens_dev
+  float* rot_pts;
+  if (!carve(workspace, workspace_bytes, cap_in, B, 0, 0, W, offs_d, rot_pts)) return -1;
   W.errflag = status_dev + 1;   // label overflow cannot happen without labels; shares the overflow word
 
-  Schedule sched;
-  sched.nb[0] = 13;
-  for (int e = 1; e < 48; ++e) sched.nb[e] = mvk_next_bkt(2 * sched.nb[e - 1]);
+  const Schedule sched = make_schedule();
   // two launches: the per-cloud kernel (offsets from the device lengths, orientation as its phase 0) and the finish
   W.lens_dev = lens_dev;
   W.rot_dev = rot_dev;

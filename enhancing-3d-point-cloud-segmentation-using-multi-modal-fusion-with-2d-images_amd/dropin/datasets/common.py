@@ -89,22 +89,25 @@ def batch_neighbors(queries, supports, q_batches, s_batches, radius, limit=None,
 
 
 def pyramid_plan(config):
-    """The radii / cell sizes segmentation_inputs_sphere uses, one dict per pyramid layer
-    (common.py:797-857): ``conv_r`` (None when the layer has no conv block), ``pool`` (whether a level
-    follows), ``dl`` of the subsampling and the pool / upsample search radii."""
+    """The radii / cell sizes of the pyramid, one dict per layer (common.py:797-857), for both builders of it
+    (segmentation_inputs_sphere below and synthetic.DeviceInputChain): ``conv_r`` (None when the layer has no conv
+    block), ``pool`` (whether a level follows), ``dl`` of the subsampling, the pool / upsample search radii and
+    ``deform`` (a conv block or the pooling block of the layer is deformable). The kernels get these Python doubles
+    rounded to float32: the order of the operations below is part of the contract."""
     r_normal = config.first_subsampling_dl * config.conv_radius
     plan, layer_blocks = [], []
     for block in config.architecture:
         if not ('pool' in block or 'strided' in block or 'global' in block or 'upsample' in block):
             layer_blocks.append(block)
             continue
-        entry = dict(conv_r=None, pool=False, dl=None, pool_r=None, up_r=None)
+        entry = dict(conv_r=None, pool=False, dl=None, pool_r=None, up_r=None, deform=False)
         if layer_blocks:
-            deform = bool(np.any(['deformable' in b for b in layer_blocks]))
-            entry['conv_r'] = r_normal * config.deform_radius / config.conv_radius if deform else r_normal
+            entry['deform'] = any('deformable' in b for b in layer_blocks)
+            entry['conv_r'] = r_normal * config.deform_radius / config.conv_radius if entry['deform'] else r_normal
         if 'pool' in block or 'strided' in block:
             r = r_normal * config.deform_radius / config.conv_radius if 'deformable' in block else r_normal
-            entry.update(pool=True, dl=2 * r_normal / config.conv_radius, pool_r=r, up_r=2 * r)
+            entry.update(pool=True, dl=2 * r_normal / config.conv_radius, pool_r=r, up_r=2 * r,
+                         deform=entry['deform'] or 'deformable' in block)
         plan.append(entry)
         r_normal *= 2
         layer_blocks = []
@@ -136,7 +139,6 @@ def segmentation_inputs_sphere(config, stacked_points, stack_lengths, neighborho
     (ops.reverse_neighbors; None elsewhere): the feature gradient of those convolutions then runs as a gather in a fixed
     summation order instead of an atomic scatter (MVK_REVERSE_DX=0: none). With ``status`` they are built at a fixed width
     and ``rev_status`` collects their overflow word (ops.check_reverse_status)."""
-    r_normal = config.first_subsampling_dl * config.conv_radius
     want_orders = os.environ.get("MVK_GATHER_ORDER", "1") != "0"
     grid_of = [None, None]          # supports tensor and radius of the grid the neighbour workspace holds
 
@@ -153,7 +155,6 @@ def segmentation_inputs_sphere(config, stacked_points, stack_lengths, neighborho
     out = dict(points=[], neighbors=[], pools=[], upsamples=[], lengths=[], deform_layers=[], orders=[],
                rev_neighbors=[], rev_pools=[])
     want_rev = ops.REVERSE_DX
-    layer_blocks = []
     level = 0
     dev = pts.device
 
@@ -165,38 +166,24 @@ def segmentation_inputs_sphere(config, stacked_points, stack_lengths, neighborho
     def empty_idx():
         return torch.zeros((0, 1), dtype=index_dtype, device=dev)
 
-    for block in config.architecture:
-        if not ('pool' in block or 'strided' in block or 'global' in block or 'upsample' in block):
-            layer_blocks.append(block)
-            continue
-        layer = len(out['points'])
-        deform_layer = False
-        if layer_blocks:
-            if np.any(['deformable' in b for b in layer_blocks]):
-                r = r_normal * config.deform_radius / config.conv_radius
-                deform_layer = True
-            else:
-                r = r_normal
-            conv_i = neighbors(pts, pts, lens, lens, r, layer)
-            order = None
+    def rev_status():                   # sync-free pyramid: fixed widths, one status word for all the reverse lists
+        if 'rev_status' not in out:
+            out['rev_status'] = torch.zeros(2, dtype=torch.int32, device=dev)
+        return out['rev_status']
+
+    for layer, e in enumerate(pyramid_plan(config)):
+        conv_i, order = empty_idx(), None
+        if e['conv_r'] is not None:
+            conv_i = neighbors(pts, pts, lens, lens, e['conv_r'], layer)
             if want_orders and pts.shape[0] > 0 and conv_i.shape[1] > 0:      # the workspace holds this search's grid
                 order = ops.neighbors_cell_order(pts.shape[0], pts.shape[0], len(lens), device=pts.device)
                 ops.remember_work_order(pts, order)      # for batch containers without an `orders` attribute
-        else:
-            conv_i = empty_idx()
-            order = None
-        if 'pool' in block or 'strided' in block:
-            dl = 2 * r_normal / config.conv_radius
+        if e['pool']:
             R = rotations[level] if rotations is not None else None
-            pool_p, pool_b = batch_grid_subsampling(pts, lens, sampleDl=dl, R=R)
+            pool_p, pool_b = batch_grid_subsampling(pts, lens, sampleDl=e['dl'], R=R)
             level += 1
-            if 'deformable' in block:
-                r = r_normal * config.deform_radius / config.conv_radius
-                deform_layer = True
-            else:
-                r = r_normal
-            pool_i = neighbors(pool_p, pts, pool_b, lens, r, layer)
-            up_i = neighbors(pts, pool_p, lens, pool_b, 2 * r, layer + 1)
+            pool_i = neighbors(pool_p, pts, pool_b, lens, e['pool_r'], layer)
+            up_i = neighbors(pts, pool_p, lens, pool_b, e['up_r'], layer + 1)
         else:
             pool_i, up_i = empty_idx(), empty_idx()
             pool_p = torch.zeros((0, 3), dtype=torch.float32, device=dev)
@@ -204,17 +191,15 @@ def segmentation_inputs_sphere(config, stacked_points, stack_lengths, neighborho
         # transposed relations for the gather-form feature gradient (ops.reverse_neighbors): rigid convolutions, and since
         # round 5 the deformable ones too (searched at the wide deform radius: rows of hundreds of entries;
         # MVK_REVERSE_DX_DEFORM=0 keeps their atomic scatter)
-        rigid = want_rev and pts.is_cuda and (not deform_layer or ops.REVERSE_DX_DEFORM)
+        rigid = want_rev and pts.is_cuda and (not e['deform'] or ops.REVERSE_DX_DEFORM)
 
         def reverse(m):
             if not rigid or m.shape[0] == 0 or m.shape[1] == 0:
                 return None
             if status is None:
                 return ops.reverse_neighbors(m, pts.shape[0])               # exact width (one read-back)
-            if 'rev_status' not in out:                                     # sync-free pyramid: fixed width, one status word
-                out['rev_status'] = torch.zeros(2, dtype=torch.int32, device=dev)
             return ops.reverse_neighbors(m, pts.shape[0], width=min(ops.reverse_width_cap(), 2 * m.shape[1] + 16),
-                                         status=out['rev_status'])
+                                         status=rev_status())
 
         out['rev_neighbors'].append(reverse(conv_i))
         out['rev_pools'].append(reverse(pool_i))
@@ -227,9 +212,7 @@ def segmentation_inputs_sphere(config, stacked_points, stack_lengths, neighborho
             if status is None:
                 rev_up = ops.reverse_neighbors(up_i, pool_p.shape[0], first_column=True)
             else:
-                if 'rev_status' not in out:
-                    out['rev_status'] = torch.zeros(2, dtype=torch.int32, device=dev)
-                rev_up = ops.reverse_neighbors(up_i, pool_p.shape[0], width=64, status=out['rev_status'], first_column=True)
+                rev_up = ops.reverse_neighbors(up_i, pool_p.shape[0], width=64, status=rev_status(), first_column=True)
             ops.remember_reverse(up_i, rev_up, first_column=True)
             out.setdefault('rev_ups', {})[layer] = rev_up
         out['points'].append(pts)
@@ -237,13 +220,9 @@ def segmentation_inputs_sphere(config, stacked_points, stack_lengths, neighborho
         out['pools'].append(pool_i)
         out['upsamples'].append(up_i)
         out['lengths'].append(torch.from_numpy(np.asarray(lens, dtype=np.int32)))
-        out['deform_layers'].append(deform_layer)
+        out['deform_layers'].append(e['deform'])
         out['orders'].append(order)
         pts, lens = pool_p, pool_b
-        r_normal *= 2
-        layer_blocks = []
-        if 'global' in block or 'upsample' in block:
-            break
     return out
 
 

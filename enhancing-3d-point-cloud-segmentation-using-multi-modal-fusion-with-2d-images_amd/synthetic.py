@@ -471,7 +471,7 @@ class DeviceInputChain:
         fused = _REV_FUSED and not ops.is_deterministic()
         pending = []
 
-        def search(ql, sl, radius, out, limit_layer, rev=None, rev_shadow=None):
+        def search(ql, sl, radius, out, rev=None, rev_shadow=None):
             nonlocal grid_of
             reuse = grid_of == (sl, np.float32(radius))
             grid_of = (sl, np.float32(radius))
@@ -490,7 +490,7 @@ class DeviceInputChain:
             e = plan[l]
             if e['conv_r'] is not None:
                 rv = static.rev_neighbors[l] if static.rev_neighbors else None
-                done = search(l, l, e['conv_r'], static.neighbors[l], l, rev=rv, rev_shadow=caps[l])
+                done = search(l, l, e['conv_r'], static.neighbors[l], rev=rv, rev_shadow=caps[l])
                 if static.orders and static.orders[l] is not None:     # the workspace holds this search's grid
                     ops.neighbors_cell_order(caps[l], caps[l], self.B, static.orders[l], self.lens[l])
                 if rv is not None and not done:
@@ -499,10 +499,10 @@ class DeviceInputChain:
                 ops.grid_subsample_dev(static.points[l], self.lens[l], e['dl'], static.points[l + 1], self.lens[l + 1],
                                        self.status, rotations_dev=self.rot[l], total_out=static._counts[l + 1])
                 rv = static.rev_pools[l] if static.rev_pools else None
-                done = search(l + 1, l, e['pool_r'], static.pools[l], l, rev=rv, rev_shadow=caps[l + 1])
+                done = search(l + 1, l, e['pool_r'], static.pools[l], rev=rv, rev_shadow=caps[l + 1])
                 if rv is not None and not done:
                     ops.reverse_neighbors(static.pools[l], caps[l], out=rv, status=self.rev_status, shadow=caps[l + 1])
-                search(l, l + 1, e['up_r'], static.upsamples[l], l + 1)
+                search(l, l + 1, e['up_r'], static.upsamples[l])
                 if l in static.rev_ups:
                     ops.reverse_neighbors(static.upsamples[l], caps[l + 1], out=static.rev_ups[l], status=self.rev_status,
                                           shadow=caps[l], first_column=True)

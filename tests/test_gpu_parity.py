@@ -220,6 +220,48 @@ def test_device_lens_variants_edge_cases(ops):
         ops.check_neighbor_status(status)
 
 
+def test_neighbor_workspace_shared_by_searches_of_different_query_counts(ops):
+    """The three users of the neighbour workspace layout on ONE workspace with different query capacities: a search,
+    a search with fewer queries that reuses its grid, and the cell-order work list -- the grid part of the layout
+    must not move with the query count."""
+    rng = np.random.default_rng(31)
+    cloud = rng.random((400, 3)).astype(np.float32)
+    lens_h = [200, 0, 200]                                               # an empty cloud in the middle
+    pts = T(np.concatenate([cloud, np.full((200, 3), 1e6, np.float32)]))           # capacity 600
+    lens = torch.tensor(lens_h, dtype=torch.int32, device="cuda")
+    q_lens = torch.tensor([200, 0, 56], dtype=torch.int32, device="cuda")         # the first 256 capacity rows
+    status = torch.zeros(2, dtype=torch.int32, device="cuda")
+
+    def search(nq, ql, reuse, **rev):
+        out = torch.full((nq, 64), -7, dtype=torch.int32, device="cuda")
+        ops.radius_neighbors_dev(pts[:nq], pts, ql, lens, 0.15, out, 600, status, reuse_grid=reuse, **rev)
+        return out
+
+    full = search(600, lens, False)                                             # (a)
+    order_a = ops.neighbors_cell_order(600, 600, 3, s_lens_dev=lens)
+    reused = search(256, q_lens, True)                                          # (b): the grid of (a)
+    order_c = ops.neighbors_cell_order(256, 600, 3, s_lens_dev=lens)            # (c)
+    fresh = search(256, q_lens, False)
+    assert torch.equal(reused, fresh) and torch.equal(reused, full[:256])
+    assert torch.equal(order_c, order_a)
+    assert sorted(order_a[:400].cpu().tolist()) == list(range(400)) and order_a[400:].cpu().tolist() == list(range(400, 600))
+    longest, overflow = status.cpu().tolist()
+    assert overflow == 0 and 1 <= longest <= 64, (longest, overflow)            # about 3 supports in range of a query
+    assert (full[400:] == 600).all() and (full[:400, 0] == torch.arange(400, device="cuda")).all()
+    # once more with the search filling the transposed relation itself
+    rev = torch.full((600, 64), -7, dtype=torch.int32, device="cuda")
+    counts = torch.zeros(600, dtype=torch.int32, device="cuda")
+    rev_status = torch.zeros(2, dtype=torch.int32, device="cuda")
+    again = search(600, lens, False, rev=rev, rev_counts=counts, rev_status=rev_status)
+    ops.reverse_finish_many([(rev, counts, 600, 600)], rev_status)
+    assert torch.equal(again, full)
+    want = ops.reverse_neighbors(full, 600, sort=True)
+    w = want.shape[1]
+    got = torch.sort(rev, 1).values
+    assert torch.equal(got[:, :w], want) and (got[:, w:] == 600).all()
+    assert rev_status.cpu().tolist() == [w, 0] and int(counts.abs().sum()) == 0
+
+
 def test_capacity_padding_kernels(ops):
     src = torch.randint(0, 50, (37, 5), dtype=torch.int32, device="cuda")
     src[::3, 2] = 50                                               # shadow index of the source
