@@ -213,9 +213,16 @@ def bn_single_launch_rows(D):
 # --------------------------------------------------------------------------------------------
 # The producer's half: a product that writes the statistics partials of its output can also FINISH them (mean, invstd,
 # running statistics, batch counter) -- the workgroup that arrives last at a column tile's counter merges the partials.
-# The op wrappers (linear, linear_pair, kpconv, upsample_cat_linear) take `bn=` (the nn.BatchNorm1d that follows) and
-# park it here around their autograd node; gemm() picks it up and reports the result, which travels with the output as
-# the third element of `_mvk_bn_stats`. The consumer's half: bn_lrelu_linear().
+# The consumer's half: bn_lrelu_linear(), the BatchNorm's apply pass inside the next product's operand load.
+# The hand-off from a product to the BatchNorm behind it is ONE record, BnStats, and it travels by argument and return value:
+#   created where the launch that wrote the partials is issued: _product() (linear, upsample_cat_linear, kpconv),
+#     _LinearPairFn (one record per output) and _KPConvFn around gemm_f32_stream (the big rigid layers; never finished).
+#     The op wrappers take `bn=` (the nn.BatchNorm1d that follows); when _finishable(bn) they hand it to their autograd
+#     node as a plain forward argument, the node hands it to the product, and the record comes back as a non-tensor
+#     output of the node;
+#   attached by the op wrapper to its output as `_mvk_bn_stats` (tests attach a plain (partials, rows) tuple by hand);
+#   read by bn_stats_of() alone, which normalises what it finds: bn_lrelu / bn_lrelu_pair (_bn_fwd_problem), bn_finished,
+#     bn_lrelu_linear.
 # MEASURED SLOWER on the one-sphere step and therefore OFF by default (MVK_BN_FOLD=1 / ops.BN_FOLD = True turn it on):
 # network chain 2.85 -> 2.94 ms with finished statistics alone, 2.96 ms with the operand fold on top (round 5,
 # profiles/r05_bn_fold_chain.txt). The last-arriver hand-off at the tail of a producing product costs
@@ -223,8 +230,26 @@ def bn_single_launch_rows(D):
 # partials) against the 2-4 us the normalising launch saves by not reducing them, and in a bottleneck block with a
 # shortcut layer the convolution's BatchNorm already shares its launch with the shortcut's.
 BN_FOLD = os.environ.get("MVK_BN_FOLD", "0") == "1"
-_FIN = {"req": None, "done": None}
-_AX = {"req": None}
+# partials [row blocks, 2, N], rows per block, finished = (mean, invstd) written by the producing launch or None
+BnStats = collections.namedtuple("BnStats", "partials rows finished", defaults=(None,))
+
+
+def bn_stats_of(t):
+    """The BnStats a producing product attached to its output t for the BatchNorm that follows, or None. A plain
+    (partials, rows[, finished]) tuple found there (attached by hand) is normalised."""
+    e = getattr(t, "_mvk_bn_stats", None)
+    return e if e is None or isinstance(e, BnStats) else BnStats(*e)
+
+
+def bn_finished(t):
+    """True when t carries BatchNorm statistics FINISHED by its producer (mean, invstd)."""
+    return getattr(bn_stats_of(t), "finished", None) is not None
+
+
+def _finishable(bn):
+    """Whether a product may finish the statistics of the BatchNorm that follows it: only training-mode modules with
+    per-rank statistics qualify; anything else keeps the separate statistics pass."""
+    return BN_FOLD and bn is not None and bn.training and _SYNC_BN["group"] is None and bn.num_features % 4 == 0
 
 
 def _fin_counters(bn, device):
@@ -238,21 +263,6 @@ def _fin_counters(bn, device):
         torch.cuda.current_stream(device).synchronize()
         bn._mvk_fin_counters = c
     return c
-
-
-def _fin_request(bn):
-    """Parks the BatchNorm that follows the product about to be issued (None: no request). Only training-mode modules
-    with per-rank statistics qualify; anything else keeps the separate statistics pass."""
-    ok = (BN_FOLD and bn is not None and bn.training and _SYNC_BN["group"] is None and bn.num_features % 4 == 0)
-    _FIN["req"] = bn if ok else None
-    _FIN["done"] = None
-
-
-def _fin_take():
-    done = _FIN["done"]
-    _FIN["req"] = None
-    _FIN["done"] = None
-    return done
 
 
 def _fin_struct(bn, N, device):
@@ -275,37 +285,45 @@ def gemm(A, B, transA=False, transB=False, out=None, accumulate=False, split_k=N
     becomes .grad), so it must not be a slice of the per-step zero arena.
     stats_n_valid (DEVICE int32 [1]): also produce the column statistics of C over its first n_valid rows for
     the BatchNorm that follows; returns (C, (partials, rows per block)) -- or (C, None) when the chosen plan
-    splits the reduction. A BatchNorm parked by _fin_request() is finished inside the launch when the product carries the
-    statistics epilogue (result in _FIN["done"]); an operand transform parked by bn_lrelu_linear() is applied to A."""
+    splits the reduction."""
+    out, st = _product(A, B, transA=transA, transB=transB, out=out, accumulate=accumulate, split_k=split_k, keep=keep,
+                       stats_n_valid=stats_n_valid)
+    if stats_n_valid is None:
+        return out
+    return out, (st[:2] if st is not None else None)
+
+
+def _product(A, B, *, transA=False, transB=False, out=None, accumulate=False, split_k=None, keep=False,
+             stats_n_valid=None, finish=None, a_transform=None):
+    """gemm() for the autograd nodes: returns (C, BnStats or None). finish: the nn.BatchNorm1d that follows (the caller
+    asked _finishable); it is finished inside the launch when the product carries the statistics epilogue, is not
+    transposed on the A side and picks its own split. a_transform (bn_lrelu_linear): the BatchNorm + LeakyReLU applied
+    to A while it is staged; A must be the transform's lazy tensor, which the launch writes on the way."""
     _dev(A, B)
     A, B = _f32c(A), _f32c(B)
     M, Kd = (A.shape[1], A.shape[0]) if transA else (A.shape[0], A.shape[1])
     N = B.shape[0] if transB else B.shape[1]
     assert (B.shape[1] if transB else B.shape[0]) == Kd, "gemm: inner dimensions differ"
-    want = stats_n_valid is not None
-    ax = _AX["req"]
-    if ax is not None:
-        _AX["req"] = None
-        if ax["lazy"].data_ptr() != A.data_ptr() or transA or not transB or out is not None or accumulate or M == 0:
-            raise RuntimeError("ops.gemm: a parked operand transform did not meet its product")
+    ax = a_transform
+    if ax is not None and (ax["lazy"].data_ptr() != A.data_ptr() or transA or not transB or out is not None or accumulate
+                           or M == 0):
+        raise RuntimeError("ops: a product with an operand transform takes the lazy tensor as A, W as transposed B and "
+                           "an output of its own")
     if M == 0 or N == 0 or Kd == 0:
-        res = out.zero_() if out is not None else torch.zeros((M, N), device=A.device, dtype=torch.float32)
-        return (res, None) if want else res
+        return (out.zero_() if out is not None else torch.zeros((M, N), device=A.device, dtype=torch.float32)), None
     split_arena_prepare(A.device)
-    req = _FIN["req"]
     # a finished BatchNorm needs the epilogue statistics whatever the row count (the one-launch BatchNorm kernels of few
     # rows would otherwise do statistics + normalisation themselves: with a fold there is no such launch)
-    stats_ok = want and out is None and not accumulate and M <= _STATS_EPILOGUE_ROWS
-    if req is None and ax is None:
+    stats_ok = stats_n_valid is not None and out is None and not accumulate and M <= _STATS_EPILOGUE_ROWS
+    if finish is None and ax is None:
         stats_ok = stats_ok and M > bn_single_launch_rows(N)
     split, rows = gemm_plan(M, N, Kd, split_k, stats_ok)
     if out is None:
         out = _split_out((M, N), A.device, split, keep)
     part = torch.empty(((M + rows - 1) // rows, 2, N), device=A.device, dtype=torch.float32) if rows > 0 else None
-    fin = None
-    if req is not None and part is not None and not transA and split_k is None:
-        fin, _FIN["done"] = _fin_struct(req, N, A.device)
-        _FIN["req"] = None
+    fin = done = None
+    if finish is not None and part is not None and not transA and split_k is None:
+        fin, done = _fin_struct(finish, N, A.device)
     if fin is not None or ax is not None:
         xf = None
         if ax is not None:
@@ -320,9 +338,7 @@ def gemm(A, B, transA=False, transB=False, out=None, accumulate=False, split_k=N
     else:
         check(lib().mvk_gemm_f32_ex(_p(A), _p(B), _p(out), M, N, Kd, int(transA), int(transB), int(accumulate),
                                     int(split), _p(part), _p(stats_n_valid) if part is not None else None, _stream()))
-    if want:
-        return out, ((part, rows) if part is not None else None)
-    return out
+    return out, (BnStats(part, rows, done) if part is not None else None)
 
 
 def gemm_f32_stream_plan(M, N, Kd):
@@ -761,7 +777,7 @@ class _KPConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, s, idx, x, kp, W, offsets, modulations, extent, influence, aggregation, stats_n_valid=None,
-                order=None, rev=None, rev_order=None):
+                order=None, rev=None, rev_order=None, finish=None):
         K, Cin, Cout = W.shape
         deform = offsets is not None
         A, min_d2 = kpconv_gather(q, s, idx, x, kp, extent, influence, aggregation, offsets, want_min_d2=deform,
@@ -773,26 +789,22 @@ class _KPConvFn(torch.autograd.Function):
         st = None
         if _contraction_streams(Am, q.shape[0], K * Cin, Cout):                 # the big rigid layers (levels 0-1)
             y, st = gemm_f32_stream(Am.view(-1, K * Cin), W.reshape(K * Cin, Cout), stats_n_valid)
-        elif stats_n_valid is not None:                                         # blocks.py:370-374
-            y, st = gemm(Am.view(-1, K * Cin), W.reshape(K * Cin, Cout), stats_n_valid=stats_n_valid)
-        else:
-            y = gemm(Am.view(-1, K * Cin), W.reshape(K * Cin, Cout))
+            st = BnStats(*st) if st is not None else None                       # (this kernel finishes nothing)
+        else:                                                                   # blocks.py:370-374
+            y, st = _product(Am.view(-1, K * Cin), W.reshape(K * Cin, Cout), stats_n_valid=stats_n_valid, finish=finish)
         if _PROF["on"]:
             e1.record()
             _PROF["gemm"].append(((q.shape[0], K * Cin, Cout), e0, e1))
         ctx.save_for_backward(q, s, idx, x, kp, W, A, offsets, modulations)
         ctx.min_arg = getattr(min_d2, "_mvk_min_arg", None)
         ctx.cfg = (extent, influence, aggregation)
-        ctx.stat_rows = st[1] if st is not None else 0
-        _LAST_STATS_ROWS[0] = ctx.stat_rows
-        part = st[0] if st is not None else None
-        if part is not None:
-            ctx.mark_non_differentiable(part)
+        if st is not None:
+            ctx.mark_non_differentiable(st.partials)
         ctx.set_materialize_grads(False)    # else autograd hands backward a ZERO tensor (one fill launch) per unused output
-        return y, min_d2, part
+        return y, min_d2, st
 
     @staticmethod
-    def backward(ctx, gy, g_min_d2, g_part=None):
+    def backward(ctx, gy, g_min_d2, g_st=None):
         q, s, idx, x, kp, W, A, offsets, modulations = ctx.saved_tensors
         extent, influence, aggregation = ctx.cfg
         K, Cin, Cout = W.shape
@@ -843,10 +855,7 @@ class _KPConvFn(torch.autograd.Function):
             dx, d_off = kpconv_scatter(q, s, idx, dA, kp, extent, influence, aggregation, x=x,
                                        offsets=offsets,
                                        g_min_d2=g_min_d2 if offsets is not None else None, min_arg=ctx.min_arg)
-        return None, None, None, dx, None, dW, d_off, d_mod, None, None, None, None, None, None, None
-
-
-_LAST_STATS_ROWS = [0]       # rows per block of the statistics partials the last KPConv forward produced
+        return None, None, None, dx, None, dW, d_off, d_mod, None, None, None, None, None, None, None, None
 
 
 def _contraction_streams(A, M, Kd, N):
@@ -858,17 +867,6 @@ def _contraction_streams(A, M, Kd, N):
     return ok and A.is_contiguous() and _slack_floats(A) >= need
 
 
-def bn_finished(t):
-    """True when t carries BatchNorm statistics FINISHED by its producer (mean, invstd; see _fin_request)."""
-    e = getattr(t, "_mvk_bn_stats", None)
-    return e is not None and len(e) > 2 and e[2] is not None
-
-
-def bn_stats_of(t):
-    """(partials, rows per block) a producing GEMM attached to its output for the BatchNorm that follows, or None."""
-    return getattr(t, "_mvk_bn_stats", None)
-
-
 def kpconv(q, s, idx, x, kp, W, extent, influence="linear", aggregation="sum", offsets=None, modulations=None,
            stats_n_valid=None, order=None, rev=None, rev_order=None, bn=None):
     """Returns (y [Nq,Cout], min_d2 [Nq,K] or None). stats_n_valid (DEVICE int32 [1]): the contraction also produces the column statistics
@@ -878,22 +876,18 @@ def kpconv(q, s, idx, x, kp, W, extent, influence="linear", aggregation="sum", o
     rev (int32 [Ns, Hr], reverse_neighbors(idx, Ns)) and rev_order (a work list of the SUPPORT level): rigid f32 layers
     with a power-of-two Cout >= 32 then compute the feature gradient as a gather over the transposed relation (fixed
     summation order, no atomics) instead of the atomic scatter.
-    bn: the nn.BatchNorm1d that normalises y; its statistics are then FINISHED by the contraction (see _fin_request)."""
+    bn: the nn.BatchNorm1d that normalises y; its statistics are then FINISHED by the contraction (when _finishable)."""
     if rev is not None and (rev.dtype != torch.int32 or rev.dim() != 2 or not rev.is_contiguous()):
         raise RuntimeError("kpconv: rev must be a contiguous int32 [Ns, Hr] matrix (ops.reverse_neighbors)")
     if influence not in INFLUENCE:
         raise ValueError("Unknown influence function type (config.KP_influence)")
     if aggregation not in AGGREGATION:
         raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
-    _fin_request(bn if stats_n_valid is not None else None)
-    try:
-        y, min_d2, part = _KPConvFn.apply(q, s, idx, x, kp, W, offsets, modulations, float(extent), influence, aggregation,
-                                   stats_n_valid, order, rev, rev_order)
-    finally:
-        fin = _fin_take()
-    if part is not None:        # rows per statistics block of the launch that just ran (set by the node's forward)
-        rows = _LAST_STATS_ROWS[0]
-        y._mvk_bn_stats = (part, rows, fin)
+    y, min_d2, st = _KPConvFn.apply(q, s, idx, x, kp, W, offsets, modulations, float(extent), influence, aggregation,
+                                    stats_n_valid, order, rev, rev_order,
+                                    bn if stats_n_valid is not None and _finishable(bn) else None)
+    if st is not None:
+        y._mvk_bn_stats = st
     return y, min_d2
 
 
@@ -1085,20 +1079,13 @@ def full_count_prepare(device):
     full_count(0, torch.device(device))
 
 
-def _ext3(ext):
-    """(partials, rows per block, finished (mean, invstd) or None) of a `_mvk_bn_stats` record (None: nothing attached)."""
-    if ext is None:
-        return None, 0, None
-    return (ext[0], ext[1], ext[2] if len(ext) > 2 else None)
-
-
 def _bn_fwd_problem(who, x, n_valid, gamma, beta, running_mean, running_var, cfg, nbt, addend, ext):
     """The arguments of mvk_bn_lrelu_fwd for x [R,D] (f32, contiguous) in the order of the export and of the fields of
-    mvk_bn_fwd_problem, cfg = (eps, momentum, slope), ext = the input's `_mvk_bn_stats` record; then y, mean, invstd and
+    mvk_bn_fwd_problem, cfg = (eps, momentum, slope), ext = the input's BnStats (bn_stats_of) or None; then y, mean, invstd and
     whatever else must stay alive until the launch has been issued."""
     R, D = x.shape
     y = torch.empty_like(x)
-    ext_part, ext_rows, fin = _ext3(ext)
+    ext_part, ext_rows, fin = ext if ext is not None else (None, 0, None)
     if ext_part is not None and (ext_part.shape[2] != D or ext_part.shape[0] != (R + ext_rows - 1) // ext_rows):
         raise RuntimeError("%s: the statistics partials do not belong to this tensor" % who)
     scratch = None
@@ -1248,8 +1235,7 @@ def bn_lrelu_linear(x, n_valid, bn, slope, W, stats_n_valid=None, bn_out=None):
     FINISHED by its producer (kpconv(..., bn=bn) / linear(..., bn=bn)). Returns (y, activations) -- the activations are
     the tensor bn_lrelu would have returned, written by the product -- or None when the fold does not apply (the caller
     then runs the two steps)."""
-    ext = bn_stats_of(x)
-    fin = ext[2] if (ext is not None and len(ext) > 2) else None
+    fin = getattr(bn_stats_of(x), "finished", None)
     R, Kd = x.shape
     if (fin is None or not BN_FOLD or _SYNC_BN["group"] is not None or not x.is_cuda or x.dtype != torch.float32
             or not x.is_contiguous() or W.dtype != torch.float32 or not W.is_contiguous() or W.shape[1] != Kd
@@ -1257,15 +1243,9 @@ def bn_lrelu_linear(x, n_valid, bn, slope, W, stats_n_valid=None, bn_out=None):
         return None
     mean, invstd = fin
     lazy = _BNLazyFn.apply(x, n_valid, bn.weight, bn.bias, mean, invstd, float(slope))
-    _AX["req"] = {"raw": x.detach(), "mean": mean, "invstd": invstd, "gamma": bn.weight.detach(), "beta": bn.bias.detach(),
-                  "slope": float(slope), "n_valid": n_valid, "lazy": lazy}
-    try:
-        y = linear(lazy, W, stats_n_valid=stats_n_valid, bn=bn_out)
-    finally:
-        pending, _AX["req"] = _AX["req"], None
-    if pending is not None:
-        raise RuntimeError("bn_lrelu_linear: the product did not take the operand transform")
-    return y, lazy
+    xf = {"raw": x.detach(), "mean": mean, "invstd": invstd, "gamma": bn.weight.detach(), "beta": bn.bias.detach(),
+          "slope": float(slope), "n_valid": n_valid, "lazy": lazy}
+    return linear(lazy, W, stats_n_valid=stats_n_valid, bn=bn_out, _a_transform=xf), lazy
 
 
 class _BNLReLUPairFn(torch.autograd.Function):
@@ -1562,7 +1542,7 @@ class _UpsampleCatLinearFn(torch.autograd.Function):
     (mvk_gemm_f32_scatter_cat) -- and the weight gradient from the saved concatenation."""
 
     @staticmethod
-    def forward(ctx, x, inds2d, skip, W, stats_n_valid):
+    def forward(ctx, x, inds2d, skip, W, stats_n_valid, finish=None):
         _dev(x, inds2d, skip, W)
         x, skip = _f32c(x), _f32c(skip)
         ctx.rev = reverse_for(inds2d, first_column=True) if is_deterministic() else None
@@ -1578,16 +1558,13 @@ class _UpsampleCatLinearFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(cat, W, inds2d)
         ctx.dims = (x.shape[0], C1, C2, stride, i64)
-        if stats_n_valid is None:
-            return gemm(cat, W, transB=True), None
-        y, st = gemm(cat, W, transB=True, stats_n_valid=stats_n_valid)
-        part = st[0] if st is not None else None
-        if part is not None:
-            ctx.mark_non_differentiable(part)
-        return y, part
+        y, st = _product(cat, W, transB=True, stats_n_valid=stats_n_valid, finish=finish)
+        if st is not None:
+            ctx.mark_non_differentiable(st.partials)
+        return y, st
 
     @staticmethod
-    def backward(ctx, g, g_part=None):
+    def backward(ctx, g, g_st=None):
         cat, W, inds2d = ctx.saved_tensors
         ns, C1, C2, stride, i64 = ctx.dims
         g = _f32c(g)
@@ -1601,7 +1578,7 @@ class _UpsampleCatLinearFn(torch.autograd.Function):
                 dx = gemm_ldb(gather_sum_rows(g, rev[:ns]), W, 0, C1, N) if ctx.needs_input_grad[0] else None
                 d_skip = gemm_ldb(g, W, C1, C2, N) if ctx.needs_input_grad[2] else None
                 dW = _dw_gemm(g, cat, target=W) if ctx.needs_input_grad[3] else None
-                return dx, None, d_skip, dW, None
+                return dx, None, d_skip, dW, None, None
             _no_reverse_list("a closest_pool / upsampling matrix")
         dx = _zeros((ns, C1), g.device)
         split = gemm_plan(M, N, Kd, None, False)[0] if M > 0 else 1
@@ -1610,18 +1587,15 @@ class _UpsampleCatLinearFn(torch.autograd.Function):
             check(lib().mvk_gemm_f32_scatter_cat(_p(g), _p(W), M, N, Kd, _p(inds2d), i64, stride, ns, C1, _p(dx),
                                                  _p(d_skip), _stream()))
         dW = _dw_gemm(g, cat, target=W) if ctx.needs_input_grad[3] else None
-        return (dx if ctx.needs_input_grad[0] else None), None, (d_skip if ctx.needs_input_grad[2] else None), dW, None
+        return (dx if ctx.needs_input_grad[0] else None), None, (d_skip if ctx.needs_input_grad[2] else None), dW, None, None
 
 
 def upsample_cat_linear(x, inds, skip, W, stats_n_valid=None, bn=None):
     """linear(upsample_cat(x, inds, skip), W, stats_n_valid=...) with a one-launch backward for x and skip."""
-    _fin_request(bn if stats_n_valid is not None else None)
-    try:
-        y, part = _UpsampleCatLinearFn.apply(x, inds, skip, W, stats_n_valid)
-    finally:
-        fin = _fin_take()
-    if part is not None:
-        y._mvk_bn_stats = (part, gemm_plan(y.shape[0], y.shape[1], W.shape[1], None, True)[1], fin)
+    y, st = _UpsampleCatLinearFn.apply(x, inds, skip, W, stats_n_valid,
+                                       bn if stats_n_valid is not None and _finishable(bn) else None)
+    if st is not None:
+        y._mvk_bn_stats = st
     return y
 
 
@@ -2403,24 +2377,22 @@ class _LinearFn(torch.autograd.Function):
     onto the buffer) instead of leaving autograd to sum two tensors with one more launch per block."""
 
     @staticmethod
-    def forward(ctx, x, W, x_is_transposed, stats_n_valid=None, passthrough=False):
+    def forward(ctx, x, W, x_is_transposed, stats_n_valid=None, passthrough=False, finish=None, a_transform=None):
         ctx.save_for_backward(x, W)
         ctx.xt = bool(x_is_transposed)
         ctx.set_materialize_grads(False)    # no zero tensors for unused gradients (statistics, an unused passthrough)
         alias = x.view_as(x) if passthrough else None
-        if stats_n_valid is None:
-            return gemm(x, W, transA=ctx.xt, transB=True), None, alias
-        y, st = gemm(x, W, transA=ctx.xt, transB=True, stats_n_valid=stats_n_valid)
-        part = st[0] if st is not None else None
-        if part is not None:
-            ctx.mark_non_differentiable(part)
-        return y, part, alias
+        y, st = _product(x, W, transA=ctx.xt, transB=True, stats_n_valid=stats_n_valid, finish=finish,
+                         a_transform=a_transform)
+        if st is not None:
+            ctx.mark_non_differentiable(st.partials)
+        return y, st, alias
 
     @staticmethod
-    def backward(ctx, g, g_part=None, g_alias=None):
+    def backward(ctx, g, g_st=None, g_alias=None):
         x, W = ctx.saved_tensors
         if g is None:
-            return g_alias, None, None, None, None
+            return g_alias, None, None, None, None, None, None
         g = _f32c(g)
         dx = dW = None
         if ctx.needs_input_grad[0]:
@@ -2439,7 +2411,7 @@ class _LinearFn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             # dW [N,Kd] = g^T [N,M] @ x [M,Kd]
             dW = _dw_gemm(g, x, transB=ctx.xt, target=W)
-        return dx, dW, None, None, None
+        return dx, dW, None, None, None, None, None
 
 
 _GEMM_DUAL = os.environ.get("MVK_GEMM_DUAL", "1") == "1"
@@ -2470,7 +2442,7 @@ class _LinearPairFn(torch.autograd.Function):
     the weight gradients go through _dw_gemm like every other layer's."""
 
     @staticmethod
-    def forward(ctx, x, W0, W1, stats_n_valid, plan):
+    def forward(ctx, x, W0, W1, stats_n_valid, plan, finish):
         M, Kd = x.shape
         N0, N1 = W0.shape[0], W1.shape[0]
         _, s0, s1, r0, r1 = plan
@@ -2479,14 +2451,10 @@ class _LinearPairFn(torch.autograd.Function):
         for N, sp, rows in ((N0, s0, r0), (N1, s1, r1)):
             outs.append(_split_out((M, N), x.device, sp))
             parts.append(torch.empty(((M + rows - 1) // rows, 2, N), device=x.device, dtype=torch.float32) if rows > 0 else None)
-        req = _FIN.get("req_pair")
-        fins = [None, None]
-        if req is not None and want:
-            done = [None, None]
-            for i, (bn, part, N) in enumerate(((req[0], parts[0], N0), (req[1], parts[1], N1))):
-                if bn is not None and part is not None:
-                    fins[i], done[i] = _fin_struct(bn, N, x.device)
-            _FIN["done_pair"] = tuple(done)
+        fins, done = [None, None], [None, None]
+        for i, (bn, part, N) in enumerate(((finish[0], parts[0], N0), (finish[1], parts[1], N1))):
+            if bn is not None and part is not None:
+                fins[i], done[i] = _fin_struct(bn, N, x.device)
         if fins[0] is not None or fins[1] is not None:
             check(lib().mvk_gemm_f32_pair_bn(_p(x), _p(W0), _p(W1), _p(outs[0]), _p(outs[1]), M, N0, N1, Kd, 1,
                                              _p(parts[0]), _p(parts[1]), _p(stats_n_valid),
@@ -2500,10 +2468,11 @@ class _LinearPairFn(torch.autograd.Function):
         for part in parts:
             if part is not None:
                 ctx.mark_non_differentiable(part)
-        return outs[0], parts[0], outs[1], parts[1]
+        st0, st1 = [BnStats(p, r, d) if p is not None else None for p, r, d in zip(parts, (r0, r1), done)]
+        return outs[0], st0, outs[1], st1
 
     @staticmethod
-    def backward(ctx, g0, gp0, g1, gp1):
+    def backward(ctx, g0, g_st0, g1, g_st1):
         x, W0, W1 = ctx.saved_tensors
         dx = dW0 = dW1 = None
         g0 = _f32c(g0) if g0 is not None else None
@@ -2520,7 +2489,7 @@ class _LinearPairFn(torch.autograd.Function):
             dW0 = _dw_gemm(g0, x, target=W0)
         if ctx.needs_input_grad[2] and g1 is not None:
             dW1 = _dw_gemm(g1, x, target=W1)
-        return dx, dW0, dW1, None, None
+        return dx, dW0, dW1, None, None, None
 
 
 def linear_pair(x, W0, W1, stats_n_valid=None, bn0=None, bn1=None):
@@ -2540,36 +2509,24 @@ def linear_pair(x, W0, W1, stats_n_valid=None, bn0=None, bn1=None):
     if not plan[0]:
         return None
     plan = tuple(int(v) for v in plan)
-
-    def ok(bn):
-        return bn if (BN_FOLD and bn is not None and bn.training and _SYNC_BN["group"] is None
-                      and bn.num_features % 4 == 0) else None
-    _FIN["req_pair"] = (ok(bn0), ok(bn1)) if want else None
-    _FIN["done_pair"] = None
-    try:
-        y0, p0, y1, p1 = _LinearPairFn.apply(x, W0, W1, stats_n_valid if want else None, plan)
-    finally:
-        done = _FIN.get("done_pair") or (None, None)
-        _FIN["req_pair"] = None
-        _FIN["done_pair"] = None
-    if p0 is not None:
-        y0._mvk_bn_stats = (p0, plan[3], done[0])
-    if p1 is not None:
-        y1._mvk_bn_stats = (p1, plan[4], done[1])
+    y0, st0, y1, st1 = _LinearPairFn.apply(x, W0, W1, stats_n_valid if want else None, plan,
+                                           tuple(bn if _finishable(bn) else None for bn in (bn0, bn1)))
+    if st0 is not None:
+        y0._mvk_bn_stats = st0
+    if st1 is not None:
+        y1._mvk_bn_stats = st1
     return y0, y1
 
 
-def linear(x, W, x_is_transposed=False, stats_n_valid=None, passthrough=False, bn=None):
+def linear(x, W, x_is_transposed=False, stats_n_valid=None, passthrough=False, bn=None, _a_transform=None):
     """nn.Linear without bias / a 1x1 convolution over rows, on gemm_f32_mfma. stats_n_valid: see kpconv().
     passthrough=True returns (y, x') with x' an alias of x whose gradient is summed into x's inside the backward GEMM
-    (use x' for the other consumer of x). bn: the nn.BatchNorm1d that follows (statistics finished by the product)."""
-    _fin_request(bn if stats_n_valid is not None else None)
-    try:
-        y, part, alias = _LinearFn.apply(x, W, x_is_transposed, stats_n_valid, passthrough)
-    finally:
-        fin = _fin_take()
-    if part is not None:        # the plan is a pure function of the shape: the same rows the product just used
-        y._mvk_bn_stats = (part, gemm_plan(y.shape[0], y.shape[1], W.shape[1], None, True)[1], fin)
+    (use x' for the other consumer of x). bn: the nn.BatchNorm1d that follows (statistics finished by the product).
+    _a_transform: bn_lrelu_linear's operand transform (x is then its lazy tensor)."""
+    y, st, alias = _LinearFn.apply(x, W, x_is_transposed, stats_n_valid, passthrough,
+                                   bn if stats_n_valid is not None and _finishable(bn) else None, _a_transform)
+    if st is not None:
+        y._mvk_bn_stats = st
     return (y, alias) if passthrough else y
 
 

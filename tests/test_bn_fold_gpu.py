@@ -4,6 +4,7 @@ BatchNorm launches and against torch. Reference semantics: KPConv-PyTorch/models
 :621-649 (ResnetBottleneckBlock: batch_norm_conv + LeakyReLU + unary2 + join). Floating point: 1e-5 on activations (the
 fold evaluates (x - mean) * (invstd * gamma) + beta, the separate launch ((x - mean) * invstd) * gamma + beta), 1e-4
 (north_star) on gradients."""
+import ctypes
 import importlib
 
 import numpy as np
@@ -193,6 +194,94 @@ def test_linear_pair_finishes_both_statistics(ops):
     for m, r in ((bn0, r0), (bn1, r1)):
         assert rel_err(m.running_var.cpu().numpy(), r.running_var.cpu().numpy()) < 1e-4
         assert int(m.num_batches_tracked) == 1
+
+
+@pytest.fixture(scope="module")
+def cloud(ops):
+    """One random cloud for the KPConv producers: 4100 points (> 4096, the fewest rows the streaming contraction takes
+    when MVK_GEMM32_STREAM=2 opens it; > 1024, so the tiled product keeps its statistics epilogue), ~8 neighbours each."""
+    rng = np.random.default_rng(9)
+    pts = torch.from_numpy((rng.random((4100, 3)) * [2.0, 2.0, 1.0]).astype(np.float32)).cuda()
+    lens = torch.tensor([4100], dtype=torch.int32)
+    idx = ops.radius_neighbors_batch(pts, pts, lens, lens, 0.125, limit=16)
+    kp = torch.from_numpy((rng.normal(size=(15, 3)) * (0.66 * 0.125 / 2)).astype(np.float32)).cuda()
+    kp[0] = 0.0
+    g = torch.Generator().manual_seed(9)
+    return pts, idx, kp, torch.randn(4100, 32, generator=g).cuda(), (torch.randn(15, 32, 32, generator=g) * 0.2).cuda()
+
+
+@pytest.mark.parametrize("fold", [False, True])
+@pytest.mark.parametrize("producer", ["linear", "upsample_cat_linear", "linear_pair", "kpconv", "kpconv_stream"])
+def test_every_producer_attaches_the_record_of_its_own_launch(ops, cloud, monkeypatch, producer, fold):
+    """The BnStats on a producer's output is the one its launch made: rows per block equal the plan function's, the
+    partials have ceil(M / rows) blocks, the statistics are finished exactly when a training BatchNorm was handed over
+    with the fold on (never by the streaming contraction), and bn_lrelu on the output equals torch's BatchNorm1d over the
+    valid rows (1e-5) either way. Shapes: the smallest with a statistics epilogue (more than bn_single_launch_rows = 1024
+    rows, unsplit plan -- asserted, not assumed)."""
+    lib_mod = importlib.import_module(PKG + "._lib")
+    g = torch.Generator().manual_seed(17)
+
+    def rand(*shape):
+        return torch.randn(*shape, generator=g).cuda()
+
+    def tiled_rows(M, N, Kd):
+        assert M > ops.bn_single_launch_rows(N)
+        split, rows = ops.gemm_plan(M, N, Kd, None, True)
+        assert split == 1 and rows > 0, "this shape has no statistics epilogue"
+        return rows
+
+    bns = [_bn(32, 1), _bn(128, 2)] if producer == "linear_pair" else [_bn(32 if "kpconv" in producer else 128, 1)]
+    refs = [_twin(bn) for bn in bns]            # before the producer runs: with the fold on IT updates the running statistics
+    ops.BN_FOLD = fold
+    try:
+        if producer == "linear":
+            M, n = 1300, 1207
+            nv = torch.tensor([n], dtype=torch.int32, device="cuda")
+            outs = [ops.linear(rand(M, 96), rand(128, 96) * 0.2, stats_n_valid=nv, bn=bns[0])]
+            rows = [tiled_rows(M, 128, 96)]
+        elif producer == "upsample_cat_linear":
+            M, n = 1300, 1300
+            nv = torch.tensor([n], dtype=torch.int32, device="cuda")
+            inds = torch.randint(0, 400, (M, 1), generator=g).cuda()
+            outs = [ops.upsample_cat_linear(rand(400, 64), inds, rand(M, 32), rand(128, 96) * 0.2, stats_n_valid=nv, bn=bns[0])]
+            rows = [tiled_rows(M, 128, 96)]
+        elif producer == "linear_pair":
+            M, n = 1300, 1250
+            nv = torch.tensor([n], dtype=torch.int32, device="cuda")
+            outs = ops.linear_pair(rand(M, 64), rand(32, 64) * 0.2, rand(128, 64) * 0.2, nv, bn0=bns[0], bn1=bns[1])
+            assert outs is not None, "the two products do not share a launch at this shape"
+            plan = (ctypes.c_int * 5)()
+            lib_mod.check(lib_mod.lib().mvk_gemm_f32_pair_plan(M, 32, 128, 64, 1, plan))
+            assert plan[0] == 1 and plan[1] == 1 and plan[2] == 1 and plan[3] > 0 and plan[4] > 0
+            rows = [plan[3], plan[4]]
+        else:
+            pts, idx, kp, x, W = cloud
+            M, n = 4100, 4000
+            nv = torch.tensor([n], dtype=torch.int32, device="cuda")
+            assert not ops.gemm_f32_stream_plan(M, 32, 480)[0]
+            if producer == "kpconv_stream":
+                monkeypatch.setenv("MVK_GEMM32_STREAM", "2")        # read per call: every supported shape streams
+                ok, tiles, _, need = ops.gemm_f32_stream_plan(M, 32, 480)
+                assert ok and need == 0
+                rows = [16 * tiles]
+            else:
+                rows = [tiled_rows(M, 32, 480)]
+            outs = [ops.kpconv(pts, pts, idx, x, kp, W, 0.125 * 1.2 / 2.5, stats_n_valid=nv, bn=bns[0])[0]]
+        for y, bn, ref, r in zip(outs, bns, refs, rows):
+            st = ops.bn_stats_of(y)
+            assert st is not None, "the producer attached no statistics"
+            assert st.rows == r
+            assert st.partials.shape == ((M + r - 1) // r, 2, bn.num_features)
+            assert (st.finished is not None) == (fold and producer != "kpconv_stream")
+            assert ops.bn_finished(y) == (st.finished is not None)
+            out = ops.bn_lrelu(y, nv, bn, slope=0.1)
+            want = torch.nn.functional.leaky_relu(ref(y[:n]), 0.1)
+            assert (out[n:] == 0).all()
+            assert rel_err(out[:n].detach().cpu().numpy(), want.detach().cpu().numpy()) < 1e-5
+            assert rel_err(bn.running_mean.cpu().numpy(), ref.running_mean.cpu().numpy()) < 1e-5
+            assert int(bn.num_batches_tracked) == 1
+    finally:
+        ops.BN_FOLD = True      # (the module fixture restores the default at the end)
 
 
 def test_resnet_block_with_and_without_the_fold(ops):
