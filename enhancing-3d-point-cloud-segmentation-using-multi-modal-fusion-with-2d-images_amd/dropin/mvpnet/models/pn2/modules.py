@@ -1,7 +1,8 @@
 """PointNet++ building blocks of the MVPNet baseline (reference mvpnet/models/pn2/modules.py) on the HIP point ops:
 farthest point sampling, ball query, grouping, 3-NN and interpolation are kernels of csrc/pn2.hip / fusion.hip; the
-shared 1x1 convolutions, BatchNorm and the max over neighbours stay PyTorch ops. Sub-module names match the reference
-so its checkpoints load."""
+shared 1x1 convolutions, BatchNorm and the max over neighbours stay PyTorch ops, except after freeze_inference, when a
+SetAbstraction or FeaturePropagation in eval mode under torch.no_grad() is its point search plus ONE fused launch
+(csrc/pn2_mlp.hip). Sub-module names match the reference so its checkpoints load."""
 import torch
 from torch import nn
 
@@ -12,6 +13,7 @@ try:
     from ...ops.ball_query import ball_query
     from ...ops.knn_distance import knn_distance
     from ...ops.interpolate import feature_interpolate
+    from ...._native import ops
 except ImportError:
     from common.nn import SharedMLP, batch_index_select
     from mvpnet.ops.fps import farthest_point_sample
@@ -19,10 +21,100 @@ except ImportError:
     from mvpnet.ops.ball_query import ball_query
     from mvpnet.ops.knn_distance import knn_distance
     from mvpnet.ops.interpolate import feature_interpolate
+    from _native import ops
 
 
 def _repr(obj, names):
     return ', '.join('{:s}={}'.format(n, getattr(obj, n)) for n in names)
+
+
+# ---------------------------------------------------------------- frozen inference
+
+def fold_chain(layers, head=None):
+    """The packed chain of the fused kernels for a stack of Conv{1,2}dBNReLU layers (and an optional final convolution
+    `head` with a bias and no activation): (params, widths) with params = [W0|b0|W1|b1|...] float32 on the layers'
+    device, W_l = conv weight * scale row-wise and b_l = conv bias * scale + shift, where scale = gamma / sqrt(running_var
+    + eps) and shift = beta - running_mean * scale (computed in float64, stored as float32). None when the stack is not
+    one the kernels run: more than three layers, a layer without ReLU or running statistics, a convolution that is not
+    1x1, widths outside ops.pn2_mlp_supported."""
+    convs = [(m.conv, m.bn, m.relu is not None) for m in layers] + ([(head, None, False)] if head is not None else [])
+    if not convs:
+        return None
+    widths, parts = [convs[0][0].in_channels], []
+    for i, (conv, bn, relu) in enumerate(convs):
+        last_linear = head is not None and i == len(convs) - 1
+        if relu == last_linear or any(k != 1 for k in conv.kernel_size) or conv.groups != 1 \
+                or conv.in_channels != widths[-1]:
+            return None
+        w = conv.weight.detach().double().reshape(conv.out_channels, conv.in_channels)
+        b = conv.bias.detach().double() if conv.bias is not None else torch.zeros_like(w[:, 0])
+        if bn is not None:
+            if bn.running_var is None or bn.running_mean is None:
+                return None
+            gamma = bn.weight.detach().double() if bn.weight is not None else torch.ones_like(b)
+            beta = bn.bias.detach().double() if bn.bias is not None else torch.zeros_like(b)
+            scale = gamma / torch.sqrt(bn.running_var.double() + bn.eps)
+            shift = beta - bn.running_mean.double() * scale
+            w, b = w * scale[:, None], b * scale + shift
+        parts += [w.reshape(-1), b]
+        widths.append(conv.out_channels)
+    if not ops.pn2_mlp_supported(widths):
+        return None
+    return torch.cat(parts).float().contiguous(), tuple(widths)
+
+
+class Freezable(object):
+    """A module with a frozen inference path. _frozen is a plain attribute (no state-dict key): None, or the snapshot
+    that _snapshot() took. train(True) drops it."""
+    _frozen = None
+
+    def _snapshot(self):
+        raise NotImplementedError
+
+    def _use_frozen(self, *tensors):
+        """The snapshot when this forward takes the frozen path: eval mode, gradients off, float32 inputs on the
+        snapshot's device."""
+        fz = self._frozen
+        if fz is None or self.training or torch.is_grad_enabled():
+            return None
+        if any(t is not None and (t.dtype != torch.float32 or t.device != fz[0].device) for t in tensors):
+            return None
+        return fz
+
+    def train(self, mode=True):
+        if mode:
+            self._frozen = None
+        return super(Freezable, self).train(mode)
+
+
+def freeze_inference(net):
+    """Snapshot, for inference, the shared MLPs of every SetAbstraction, FeaturePropagation and PN2SSG under `net` (an
+    MVPNet3D is reached through its net_3d): BatchNorm's running statistics folded into the 1x1 convolutions in
+    float64, packed as float32 (fold_chain). In eval mode under torch.no_grad() a SetAbstraction with centroids is then
+    farthest point sampling, centroid select, ball query and ONE ops.pn2_sa_mlp_max launch (grouping, concatenation,
+    the MLP and the max over the neighbours; the (B,C,M,K) tensor is never written), a FeaturePropagation with three
+    neighbours is the 3-NN search, the weight arithmetic and ONE ops.pn2_fp_mlp launch, and PN2SSG's mlp_seg + seg_logit
+    are one ops.pn2_fp_mlp launch (dropout is the identity in eval mode). In training mode, with gradients enabled, or
+    on inputs that are not float32, nothing changes. Modules the kernels do not cover stay as they are: num_centroids
+    == 0, num_neighbors == 0, stacks of more than three layers, widths outside ops.pn2_mlp_supported.
+
+    The snapshot is a plain attribute, not a buffer: state-dict keys stay as they are. It is a copy: after
+    load_state_dict (or any other change of the parameters or running statistics, or a move to another device) call
+    freeze_inference again. train(True) on a module drops its snapshot; unfreeze_inference drops all of them.
+    Returns net."""
+    with torch.no_grad():
+        for m in net.modules():
+            if isinstance(m, Freezable):
+                m._frozen = m._snapshot()
+    return net
+
+
+def unfreeze_inference(net):
+    """Drop every snapshot of freeze_inference. Returns net."""
+    for m in net.modules():
+        if isinstance(m, Freezable):
+            m._frozen = None
+    return net
 
 
 class QueryGrouper(nn.Module):
@@ -50,7 +142,7 @@ class QueryGrouper(nn.Module):
         return _repr(self, ['radius', 'max_neighbors'])
 
 
-class SetAbstraction(nn.Module):
+class SetAbstraction(Freezable, nn.Module):
     """PointNet++ set abstraction: sample centroids, group, shared MLP, max over the neighbours.
     num_centroids: 0 = one group around the origin holding every point, -1 = every point is a centroid."""
 
@@ -69,6 +161,15 @@ class SetAbstraction(nn.Module):
 
     def forward(self, xyz, feature=None):
         """xyz (B,3,N), feature (B,C,N) or None -> new_xyz (B,3,M), new_feature (B,out_channels,M)."""
+        frozen = self._use_frozen(xyz, feature)
+        if frozen is not None:
+            if self.num_centroids == -1:
+                new_xyz = xyz
+            else:
+                new_xyz = batch_index_select(xyz, farthest_point_sample(xyz, self.num_centroids), dim=2)
+            index = ball_query(new_xyz, xyz, self.radius, self.max_neighbors)
+            return new_xyz, ops.pn2_sa_mlp_max(xyz.contiguous(), None if feature is None else feature.contiguous(),
+                                               new_xyz.contiguous(), index, *frozen)
         if self.num_centroids == 0:
             assert feature is not None
             new_xyz = xyz.new_zeros([xyz.size(0), 3, 1])
@@ -86,6 +187,9 @@ class SetAbstraction(nn.Module):
         new_feature = self.mlp(group_feature)
         return new_xyz, torch.max(new_feature, dim=3)[0]
 
+    def _snapshot(self):
+        return None if self.num_centroids == 0 else fold_chain(self.mlp)
+
     def extra_repr(self):
         return _repr(self, ['num_centroids', 'radius', 'max_neighbors', 'use_xyz'])
 
@@ -101,20 +205,25 @@ class FeatureInterpolator(nn.Module):
     def forward(self, query_xyz, key_xyz, query_feature, key_feature):
         """query_xyz (B,3,N1), key_xyz (B,3,N2), query_feature (B,C1,N1) or None, key_feature (B,C2,N2)
         -> (B,C2+C1,N1)."""
-        with torch.no_grad():
-            index, distance = knn_distance(query_xyz, key_xyz, self.num_neighbors)
-            inv_distance = 1.0 / torch.clamp(distance, min=self._eps)
-            weight = inv_distance / torch.sum(inv_distance, dim=2, keepdim=True)
+        index, weight = self.weights(query_xyz, key_xyz)
         new_feature = feature_interpolate(key_feature, index, weight)
         if query_feature is not None:
             new_feature = torch.cat([new_feature, query_feature], dim=1)
         return new_feature
 
+    def weights(self, query_xyz, key_xyz):
+        """The nearest keys of every query and their normalised inverse squared distances: index, weight (B,N1,k)."""
+        with torch.no_grad():
+            index, distance = knn_distance(query_xyz, key_xyz, self.num_neighbors)
+            inv_distance = 1.0 / torch.clamp(distance, min=self._eps)
+            weight = inv_distance / torch.sum(inv_distance, dim=2, keepdim=True)
+        return index, weight
+
     def extra_repr(self):
         return _repr(self, ['num_neighbors'])
 
 
-class FeaturePropagation(nn.Module):
+class FeaturePropagation(Freezable, nn.Module):
     """PointNet++ feature propagation: interpolate the sparse level's features onto the dense level (num_neighbors 3),
     or broadcast a single global feature (num_neighbors 0), then a shared MLP."""
 
@@ -130,7 +239,15 @@ class FeaturePropagation(nn.Module):
         else:
             raise ValueError('Expected value 3, but {} given.'.format(num_neighbors))
 
+    def _snapshot(self):
+        return None if self.interpolator is None else fold_chain(self.mlp)
+
     def forward(self, dense_xyz, sparse_xyz, dense_feature, sparse_feature):
+        frozen = self._use_frozen(dense_xyz, sparse_xyz, dense_feature, sparse_feature)
+        if frozen is not None:
+            index, weight = self.interpolator.weights(dense_xyz, sparse_xyz)
+            return ops.pn2_fp_mlp(sparse_feature.contiguous(), index, weight.contiguous(),
+                                  None if dense_feature is None else dense_feature.contiguous(), *frozen)
         if self.interpolator is None:
             assert sparse_xyz.size(2) == 1 and sparse_feature.size(2) == 1
             new_feature = torch.cat([sparse_feature.expand(-1, -1, dense_xyz.size(2)), dense_feature], dim=1)

@@ -1,19 +1,23 @@
 """PointNet++ with single-scale grouping, the 3D network of the MVPNet baseline (reference
 mvpnet/models/pn2/pn2ssg.py; Qi et al., arXiv:1706.02413). Constructor arguments, defaults and sub-module names
-(sa_modules.N.mlp.M.conv, fp_modules, mlp_seg, seg_logit) are the reference's, so its checkpoints load."""
+(sa_modules.N.mlp.M.conv, fp_modules, mlp_seg, seg_logit) are the reference's, so its checkpoints load.
+freeze_inference / unfreeze_inference (modules.py) switch the fused inference forward on and off."""
 import numpy as np
 import torch
 from torch import nn
 
 try:
     from ....common.nn import SharedMLPDO, xavier_uniform
-    from .modules import SetAbstraction, FeaturePropagation
+    from .modules import SetAbstraction, FeaturePropagation, Freezable, fold_chain, freeze_inference, unfreeze_inference
+    from ...._native import ops
 except ImportError:
     from common.nn import SharedMLPDO, xavier_uniform
-    from mvpnet.models.pn2.modules import SetAbstraction, FeaturePropagation
+    from mvpnet.models.pn2.modules import (SetAbstraction, FeaturePropagation, Freezable, fold_chain, freeze_inference,
+                                           unfreeze_inference)
+    from _native import ops
 
 
-class PN2SSG(nn.Module):
+class PN2SSG(Freezable, nn.Module):
     def __init__(self,
                  in_channels,
                  num_classes,
@@ -67,7 +71,13 @@ class PN2SSG(nn.Module):
         up = feats[-1]
         for lv, fp in enumerate(self.fp_modules):
             up = fp(xyzs[-2 - lv], xyzs[-1 - lv], feats[-2 - lv], up)
+        frozen = self._use_frozen(up)
+        if frozen is not None:      # mlp_seg + seg_logit in one launch; dropout is the identity in eval mode
+            return {'seg_logit': ops.pn2_fp_mlp(None, None, None, up.contiguous(), *frozen, relu_last=False)}
         return {'seg_logit': self.seg_logit(self.mlp_seg(up))}
+
+    def _snapshot(self):
+        return fold_chain(self.mlp_seg, head=self.seg_logit)
 
     def reset_parameters(self):
         for m in self.modules():

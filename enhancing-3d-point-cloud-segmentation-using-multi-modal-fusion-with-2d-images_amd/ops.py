@@ -2345,6 +2345,106 @@ def feature_interpolate(feature, index, weight):
 
 
 # --------------------------------------------------------------------------------------------
+# MVPNet baseline, frozen inference: group / interpolate, shared MLP and max in one launch (csrc/pn2_mlp.hip)
+# --------------------------------------------------------------------------------------------
+
+def pn2_mlp_supported(widths):
+    """Whether the fused chain kernels take these widths (input width, then one per layer): the library's own rule
+    (mvk_pn2_mlp_supported, a host function, no GPU call) -- at most three layers, input rows of at most 768 values,
+    layers of at most 512, and the two activation buffers of a 32-row tile within 160 KiB of LDS."""
+    widths = [int(w) for w in widths]
+    if len(widths) < 2:
+        return False
+    return bool(lib().mvk_pn2_mlp_supported((C.c_int * len(widths))(*widths), len(widths) - 1))
+
+
+def _pn2_mlp_args(name, floats, index, params, widths):
+    """The refusals shared by pn2_sa_mlp_max and pn2_fp_mlp (dtype, layout and autograd first, then residence, so each
+    can be told apart on any tensor); returns the widths as a list and as the host array of the C call."""
+    for t in list(floats) + [params]:
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise RuntimeError("%s: floating operands must be float32 (got %s)" % (name, t.dtype))
+        if not t.is_contiguous():
+            raise RuntimeError("%s: operands must be contiguous" % name)
+        if t.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError("%s has no backward: call it under torch.no_grad() or on detached tensors" % name)
+    if index is not None:
+        if index.dtype != torch.int64:
+            raise RuntimeError("%s: index must be int64" % name)
+        if not index.is_contiguous():
+            raise RuntimeError("%s: operands must be contiguous" % name)
+    _dev(index, params, *floats)
+    widths = [int(w) for w in widths]
+    if len(widths) < 2 or min(widths) < 1:
+        raise RuntimeError("%s: widths must hold the input width and one positive width per layer" % name)
+    need = sum(widths[l + 1] * (widths[l] + 1) for l in range(len(widths) - 1))
+    if params.dim() != 1 or params.numel() != need:
+        raise RuntimeError("%s: params must be the packed chain [W0|b0|W1|b1|...] of %d values for widths %s (got %s)"
+                           % (name, need, widths, tuple(params.shape)))
+    return widths, (C.c_int * len(widths))(*widths)
+
+
+def pn2_sa_mlp_max(xyz, feature, new_xyz, index, params, widths):
+    """A frozen SetAbstraction after its ball query, as one launch: xyz (B,3,N), feature (B,C,N) or None, new_xyz (B,3,M),
+    index (B,M,K) int64 -> (B,widths[-1],M), the maximum over k of the chain relu(W_l x + b_l) applied to the row
+    [feature[:, index] | xyz[:, index] - new_xyz]. The row holds the coordinates when widths[0] == C + 3 and the features
+    alone when widths[0] == C. params: the packed float32 chain [W0|b0|W1|b1|...], W_l (widths[l+1], widths[l]); at most
+    three layers. An index outside [0, N) reads as zero before the centroid is subtracted, like group_points. No
+    autograd, no host synchronisation, no allocation but the output."""
+    widths, w_host = _pn2_mlp_args("pn2_sa_mlp_max", (xyz, feature, new_xyz), index, params, widths)
+    if xyz.dim() != 3 or xyz.shape[1] != 3 or new_xyz.dim() != 3 or new_xyz.shape[1] != 3 or index.dim() != 3 \
+            or new_xyz.shape[0] != xyz.shape[0] or tuple(index.shape[:2]) != (xyz.shape[0], new_xyz.shape[2]) \
+            or (feature is not None and (feature.dim() != 3 or feature.shape[0] != xyz.shape[0]
+                                         or feature.shape[2] != xyz.shape[2])):
+        raise RuntimeError("pn2_sa_mlp_max: expected xyz (B,3,N), feature (B,C,N) or None, new_xyz (B,3,M), index (B,M,K)")
+    B, _, N = xyz.shape
+    M, K = index.shape[1], index.shape[2]
+    Cf = feature.shape[1] if feature is not None else 0
+    if widths[0] not in ((Cf + 3, Cf) if Cf else (3,)):
+        raise RuntimeError("pn2_sa_mlp_max: widths[0] = %d, the input rows hold %d features (+ 3 coordinates)"
+                           % (widths[0], Cf))
+    out = torch.empty((B, widths[-1], M), device=xyz.device, dtype=torch.float32)
+    check(lib().mvk_pn2_sa_fwd(_p(xyz), _p(feature), _p(new_xyz), _p(index), _p(params), w_host, len(widths) - 1, B, Cf,
+                               int(widths[0] == Cf + 3), N, M, K, _p(out), _stream()))
+    return out
+
+
+def pn2_fp_mlp(sparse, index, weight, dense, params, widths, relu_last=True):
+    """A frozen FeaturePropagation after its 3-NN search, or a plain shared MLP, as one launch: sparse (B,C2,N2), index
+    (B,N1,3) int64, weight (B,N1,3), dense (B,C1,N1) or None -> (B,widths[-1],N1), the chain applied to the row
+    [interpolated (C2) | dense (C1)]; the interpolated values are feature_interpolate's bit for bit. index None: the row
+    is `dense` alone (sparse and weight are ignored). relu_last False: the last layer is linear (logits). params, widths
+    and the rest as pn2_sa_mlp_max."""
+    if index is None:
+        sparse = weight = None
+    widths, w_host = _pn2_mlp_args("pn2_fp_mlp", (sparse, weight, dense), index, params, widths)
+    if index is None:
+        if dense is None or dense.dim() != 3:
+            raise RuntimeError("pn2_fp_mlp: without an index, dense (B,C1,N1) is the input")
+        B, C2, N2 = dense.shape[0], 0, 0
+    else:
+        if sparse is None or weight is None or sparse.dim() != 3 or index.dim() != 3 or index.shape[2] != 3 \
+                or tuple(weight.shape) != tuple(index.shape) or index.shape[0] != sparse.shape[0] \
+                or (dense is not None and (dense.dim() != 3 or dense.shape[0] != sparse.shape[0]
+                                           or dense.shape[2] != index.shape[1])):
+            raise RuntimeError("pn2_fp_mlp: expected sparse (B,C2,N2), index (B,N1,3), weight (B,N1,3), dense (B,C1,N1) "
+                               "or None")
+        B, C2, N2 = sparse.shape
+    N1 = index.shape[1] if index is not None else dense.shape[2]
+    C1 = dense.shape[1] if dense is not None else 0
+    if widths[0] != C2 + C1:
+        raise RuntimeError("pn2_fp_mlp: widths[0] = %d, the input rows hold %d + %d values" % (widths[0], C2, C1))
+    dev = dense.device if dense is not None else sparse.device
+    out = torch.empty((B, widths[-1], N1), device=dev, dtype=torch.float32)
+    status = pn2_index_status(dev) if index is not None else None
+    check(lib().mvk_pn2_fp_fwd(_p(sparse), _p(index), _p(weight), _p(dense), _p(params), w_host, len(widths) - 1,
+                               int(bool(relu_last)), B, C2, C1, N2, N1, _p(out), _p(status), _stream()))
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # fused FeatureAggregation path: gather kernel + MFMA linear layers
 # --------------------------------------------------------------------------------------------
 

@@ -718,6 +718,38 @@ int mvk_interpolate_bwd(const float* grad_out, const int64_t* index, const float
 int mvk_interpolate_bwd_f64(const double* grad_out, const int64_t* index, const double* weight, int B, int C, int64_t N1,
                             int64_t N2, double* grad_in, int32_t* status, void* stream);
 
+/* ---------------- Frozen PointNet++ inference: group / interpolate, shared MLP, max (csrc/pn2_mlp.hip) ------------- */
+/* Both entry points run a chain of n_layers (1 .. 3) layers y = relu(W_l x + b_l) on rows they assemble on chip, float32
+ * only, forward only. params (DEVICE) is the packed chain [W_0 | b_0 | W_1 | b_1 | ...] with W_l [widths[l+1], widths[l]]
+ * row-major (a BatchNorm already folded into its rows) and b_l [widths[l+1]]; widths_host (HOST) holds the n_layers + 1
+ * widths, widths_host[0] being the length of an input row. Products are v_mfma_f32_16x16x4_f32: per output
+ * one fma chain over k in ascending order that starts from the bias. Supported: input rows of up to 768 values, layers
+ * of up to 512, and the two on-chip activation buffers of a 32-row tile (rows padded to multiples of 16, plus 4) within
+ * 160 KiB; anything else is refused. Nothing of size rows x channels is written except `out`. One launch, no host
+ * synchronisation, no workspace: capturable.
+ *
+ * mvk_pn2_mlp_supported: 1 when both entry points take a chain of these widths, else 0 (and mvk_last_error says why); a
+ * host function, no GPU call.
+ *
+ * Set abstraction: xyz [B,3,N], feature [B,C,N] or NULL, new_xyz [B,3,M], index [B,M,K] int64 (a ball query's) ->
+ * out [B,widths[n_layers],M] = max over k of the chain applied to the row [feature[:, index] | xyz[:, index] - new_xyz]
+ * (features first; the coordinates are present when use_xyz != 0 or feature is NULL). An index outside [0, N) reads as
+ * zero for the features and for xyz BEFORE the centroid is subtracted (mvk_group_points_fwd followed by the
+ * subtraction); such a row takes part in the maximum. K >= 1. */
+int mvk_pn2_mlp_supported(const int* widths_host, int n_layers);
+int mvk_pn2_sa_fwd(const float* xyz, const float* feature, const float* new_xyz, const int64_t* index, const float* params,
+                   const int* widths_host, int n_layers, int B, int C, int use_xyz, int64_t N, int64_t M, int K, float* out,
+                   void* stream);
+/* Propagation and head: sparse_feature [B,C2,N2], index [B,N1,3] int64, weight [B,N1,3], dense_feature [B,C1,N1] or
+ * NULL -> out [B,widths[n_layers],N1] = the chain applied to the row [interpolated (C2) | dense (C1)]. The interpolated
+ * values are those of mvk_interpolate_fwd bit for bit (k = 0, 1, 2 in order, rounded products and sums; an index outside
+ * [0, N2) contributes nothing and sets *status, int32 on the device or NULL, to 1). index == NULL: the row is
+ * dense_feature alone (sparse_feature, weight, C2 and N2 are ignored). relu_last == 0: the last layer is linear (the
+ * segmentation head's logits). */
+int mvk_pn2_fp_fwd(const float* sparse_feature, const int64_t* index, const float* weight, const float* dense_feature,
+                   const float* params, const int* widths_host, int n_layers, int relu_last, int B, int C2, int C1,
+                   int64_t N2, int64_t N1, float* out, int32_t* status, void* stream);
+
 /* ---------------- PointNet++ backwards in a fixed order (csrc/pn2_ordered.hip) ------------------------- */
 /* feature_interpolate and group_points select keys in [0, N1) through an int64 index [B,N2,K] (K = 3 for the
  * interpolation): per batch element a flat list of L = N2*K positions p = n*K + k. Their backwards below are gathers
