@@ -158,6 +158,10 @@ _SIGNATURES = {
     "mvk_fps_f64": (C.c_int, [_vp, _i, _i64, _i, _i64, _vp, _vp, _i64, _vp]),
     "mvk_pn2_ball_query": (C.c_int, [_vp, _vp, _i, _i64, _i64, _f, _i, _vp, _vp, _vp]),
     "mvk_pn2_ball_query_f64": (C.c_int, [_vp, _vp, _i, _i64, _i64, _f, _i, _vp, _vp, _vp]),
+    "mvk_fps_ragged": (C.c_int, [_vp, _vp, _i, _i64, _i, _i64, _vp, _vp, _i64, _vp]),
+    "mvk_fps_ragged_f64": (C.c_int, [_vp, _vp, _i, _i64, _i, _i64, _vp, _vp, _i64, _vp]),
+    "mvk_pn2_ball_query_ragged": (C.c_int, [_vp, _vp, _vp, _i, _i64, _i64, _f, _i, _vp, _vp, _vp]),
+    "mvk_pn2_ball_query_ragged_f64": (C.c_int, [_vp, _vp, _vp, _i, _i64, _i64, _f, _i, _vp, _vp, _vp]),
     "mvk_knn_distance": (C.c_int, [_vp, _vp, _i, _i64, _i64, _i, _vp, _vp, _vp]),
     "mvk_knn_distance_f64": (C.c_int, [_vp, _vp, _i, _i64, _i64, _i, _vp, _vp, _vp]),
     "mvk_interpolate_fwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _vp]),

@@ -18,6 +18,16 @@
 //                  (bitreverse << 23) | j, smaller wins; blockDim is a power of two >= Bk, so all points of one lane
 //                  share j mod Bk and the in-lane scan in ascending j with a strict > is the rule restricted to a lane.
 //                  A point at distance 0 never wins; when no point has a positive distance the index is repeated.
+//   Ragged form   (mvk_fps_ragged, mvk_pn2_ball_query_ragged): `lengths` [B] int64 or null. Cloud b is the rows [0, n_b)
+//                  of its padded [N] block, n_b = clamp(lengths[b], 1, N): one load per workgroup (per wave in the ball
+//                  query), uniform over the wave. Rows at or beyond n_b are never read. Thread count, points per lane,
+//                  workspace and lb stay those of the padded N; the picks are still those of the n_b-point cloud alone:
+//                  for j < n <= N the key built from Bk(N) orders points as the key from Bk(n) does. Bk(n) divides
+//                  Bk(N), so bitreverse(j mod Bk(N)) has bitreverse(j mod Bk(n)) in its top bits, and what follows below
+//                  them are the bits of j above log2 Bk(n), reversed. Below the cap of 512, n < 2 Bk(n): j < n has at most
+//                  one such bit, and both keys compare it last (as that bit here, as part of j there). At the cap
+//                  Bk(n) = Bk(N) = 512. Below 16 points Bk(n) = 16 > j, and the key from Bk(N) is bitreverse(j, 4)
+//                  followed by zeros. (tests/test_pn2_ragged_cpu.py checks this on lattice clouds.)
 //   ball_query_k   one wave per query, 64 consecutive keys per round: ballot, prefix popcount, ordered write; stops once
 //                  K hits are found. No barrier (a wave leaves early on its own).
 //   knn3_k         one lane per query, key tiles staged in LDS, three sorted slots updated by strict-< insertion.
@@ -107,22 +117,30 @@ __device__ __forceinline__ bool fps_pick(FpsShared<T>& sh, int buf, T bd, uint32
   return true;
 }
 
+// The point count of cloud b: N without `lengths`, else lengths[b] clamped to [1, N] (see "Ragged form" above).
+__device__ __forceinline__ int64_t ragged_len(const int64_t* __restrict__ lengths, int64_t b, int64_t N) {
+  if (!lengths) return N;
+  const int64_t n = lengths[b];
+  return n < 1 ? 1 : (n > N ? N : n);
+}
+
 __device__ __forceinline__ uint32_t fps_rev(int64_t j, int lb) {
   return __brev((uint32_t)j & ((1u << lb) - 1)) >> (32 - lb);
 }
 
 template <typename T, int D, int PPL>
-__global__ __launch_bounds__(FPS_MAX_T) void fps_reg_k(const T* __restrict__ points, int64_t N, int64_t M, int lb,
-                                                       int64_t* __restrict__ index) {
+__global__ __launch_bounds__(FPS_MAX_T) void fps_reg_k(const T* __restrict__ points, const int64_t* __restrict__ lengths,
+                                                       int64_t N, int64_t M, int lb, int64_t* __restrict__ index) {
   __shared__ FpsShared<T> sh;
   const int t = threadIdx.x, nt = blockDim.x;
   const T* P = points + (int64_t)blockIdx.x * N * D;
   int64_t* out = index + (int64_t)blockIdx.x * M;
+  const int64_t nb = ragged_len(lengths, blockIdx.x, N);
   T px[PPL], py[PPL], pz[PPL], run[PPL];
 #pragma unroll
   for (int i = 0; i < PPL; ++i) {
     const int64_t j = t + (int64_t)i * nt;
-    const bool valid = j < N;
+    const bool valid = j < nb;
     px[i] = valid ? P[j * D] : (T)0;
     py[i] = valid ? P[j * D + 1] : (T)0;
     pz[i] = (valid && D == 3) ? P[j * D + 2] : (T)0;
@@ -155,13 +173,15 @@ __global__ __launch_bounds__(FPS_MAX_T) void fps_reg_k(const T* __restrict__ poi
 }
 
 template <typename T, int D>
-__global__ __launch_bounds__(FPS_MAX_T) void fps_ws_k(const T* __restrict__ points, int64_t N, int64_t M, int lb,
-                                                      T* __restrict__ ws, int64_t* __restrict__ index) {
+__global__ __launch_bounds__(FPS_MAX_T) void fps_ws_k(const T* __restrict__ points, const int64_t* __restrict__ lengths,
+                                                      int64_t N, int64_t M, int lb, T* __restrict__ ws,
+                                                      int64_t* __restrict__ index) {
   __shared__ FpsShared<T> sh;
   const int t = threadIdx.x, nt = blockDim.x;
   const T* P = points + (int64_t)blockIdx.x * N * D;
   T* run = ws + (int64_t)blockIdx.x * N;
   int64_t* out = index + (int64_t)blockIdx.x * M;
+  const int64_t nb = ragged_len(lengths, blockIdx.x, N);
   const uint32_t rev = fps_rev(t, lb) << FPS_J_BITS;
   int64_t cur = 0;
   T cx = P[0], cy = P[1], cz = D == 3 ? P[2] : (T)0;
@@ -169,7 +189,7 @@ __global__ __launch_bounds__(FPS_MAX_T) void fps_ws_k(const T* __restrict__ poin
   for (int64_t r = 1; r < M; ++r) {
     T bd = (T)0, bx = (T)0, by = (T)0, bz = (T)0;
     int64_t bj = 0;
-    for (int64_t j = t; j < N; j += nt) {                            // a slot of `run` is only ever touched by its lane
+    for (int64_t j = t; j < nb; j += nt) {                           // a slot of `run` is only ever touched by its lane
       const T x = P[j * D], y = P[j * D + 1], z = D == 3 ? P[j * D + 2] : (T)0;
       T d = dist2<T, D>(x, y, z, cx, cy, cz);
       if (r > 1) {
@@ -196,8 +216,9 @@ __global__ __launch_bounds__(FPS_MAX_T) void fps_ws_k(const T* __restrict__ poin
 constexpr int BQ_T = 256;                            // 4 waves = 4 queries per workgroup
 
 template <typename T>
-__global__ __launch_bounds__(BQ_T) void ball_query_k(const T* __restrict__ query, const T* __restrict__ key, int64_t total,
-                                                     int64_t N1, int64_t N2, T r2, int K, int64_t* __restrict__ index,
+__global__ __launch_bounds__(BQ_T) void ball_query_k(const T* __restrict__ query, const T* __restrict__ key,
+                                                     const int64_t* __restrict__ lengths, int64_t total, int64_t N1,
+                                                     int64_t N2, T r2, int K, int64_t* __restrict__ index,
                                                      T* __restrict__ distance) {
   const int lane = threadIdx.x & 63;
   const int64_t q = (int64_t)blockIdx.x * (BQ_T / 64) + (threadIdx.x >> 6);
@@ -205,15 +226,16 @@ __global__ __launch_bounds__(BQ_T) void ball_query_k(const T* __restrict__ query
   const int64_t b = q / N1;
   const T qx = query[q * 3], qy = query[q * 3 + 1], qz = query[q * 3 + 2];
   const T* Kp = key + b * N2 * 3;
+  const int64_t nb = ragged_len(lengths, b, N2);       // the keys of batch element b: rows [0, nb)
   int64_t* out = index + q * K;
   T* dout = distance ? distance + q * K : nullptr;
   int cnt = 0;
   int64_t first = -1;
-  for (int64_t base = 0; base < N2 && cnt < K; base += 64) {
+  for (int64_t base = 0; base < nb && cnt < K; base += 64) {
     const int64_t j = base + lane;
     bool hit = false;
     T d = (T)0;
-    if (j < N2) {
+    if (j < nb) {
       d = dist2<T, 3>(Kp[j * 3], Kp[j * 3 + 1], Kp[j * 3 + 2], qx, qy, qz);
       hit = d < r2;
     }
@@ -355,12 +377,13 @@ inline int64_t fps_workspace_bytes(int64_t B, int64_t N) {
 }
 
 template <typename T, int D>
-int fps_launch(const T* points, int B, int64_t N, int64_t M, int64_t* index, void* ws, int64_t ws_bytes, hipStream_t st) {
+int fps_launch(const T* points, const int64_t* lengths, int B, int64_t N, int64_t M, int64_t* index, void* ws,
+               int64_t ws_bytes, hipStream_t st) {
   const int lb = fps_ref_log2_block(N), nt = fps_threads(N);
   const int64_t ppl = cdiv64(N, nt);
 #define MVK_FPS_REG(P)                                                                                            \
   if (ppl <= P) {                                                                                                 \
-    hipLaunchKernelGGL((fps_reg_k<T, D, P>), dim3((unsigned)B), dim3(nt), 0, st, points, N, M, lb, index);        \
+    hipLaunchKernelGGL((fps_reg_k<T, D, P>), dim3((unsigned)B), dim3(nt), 0, st, points, lengths, N, M, lb, index); \
     MVK_CHECK_HIP(hipGetLastError());                                                                             \
     return 0;                                                                                                     \
   }
@@ -375,14 +398,15 @@ int fps_launch(const T* points, int B, int64_t N, int64_t M, int64_t* index, voi
   const int64_t need = fps_workspace_bytes<T>(B, N);
   MVK_REQUIRE(ws && ws_bytes >= need, "fps: %lld points per cloud need a workspace of %lld bytes (got %lld)",
               (long long)N, (long long)need, (long long)ws_bytes);
-  hipLaunchKernelGGL((fps_ws_k<T, D>), dim3((unsigned)B), dim3(FPS_MAX_T), 0, st, points, N, M, lb, (T*)ws, index);
+  hipLaunchKernelGGL((fps_ws_k<T, D>), dim3((unsigned)B), dim3(FPS_MAX_T), 0, st, points, lengths, N, M, lb, (T*)ws,
+                     index);
   MVK_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
 template <typename T>
-int fps_entry(const T* points, int B, int64_t N, int D, int64_t M, int64_t* index, void* ws, int64_t ws_bytes,
-              void* stream) {
+int fps_entry(const T* points, const int64_t* lengths, int B, int64_t N, int D, int64_t M, int64_t* index, void* ws,
+              int64_t ws_bytes, void* stream) {
   MVK_REQUIRE(B >= 0 && N >= 1 && N < ((int64_t)1 << FPS_J_BITS), "fps: bad sizes B=%d N=%lld (1 <= N < 2^%d)", B,
               (long long)N, FPS_J_BITS);
   MVK_REQUIRE(D == 2 || D == 3, "fps: only 2-D and 3-D points (got D=%d)", D);
@@ -390,13 +414,13 @@ int fps_entry(const T* points, int B, int64_t N, int D, int64_t M, int64_t* inde
   if (B == 0) return 0;
   MVK_REQUIRE(points && index, "fps: null operand");
   hipStream_t st = (hipStream_t)stream;
-  return D == 3 ? fps_launch<T, 3>(points, B, N, M, index, ws, ws_bytes, st)
-                : fps_launch<T, 2>(points, B, N, M, index, ws, ws_bytes, st);
+  return D == 3 ? fps_launch<T, 3>(points, lengths, B, N, M, index, ws, ws_bytes, st)
+                : fps_launch<T, 2>(points, lengths, B, N, M, index, ws, ws_bytes, st);
 }
 
 template <typename T>
-int ball_query_entry(const T* query, const T* key, int B, int64_t N1, int64_t N2, float radius, int K, int64_t* index,
-                     T* distance, void* stream) {
+int ball_query_entry(const T* query, const T* key, const int64_t* lengths, int B, int64_t N1, int64_t N2, float radius,
+                     int K, int64_t* index, T* distance, void* stream) {
   MVK_REQUIRE(B >= 0 && N1 >= 0 && N2 >= 1 && K >= 1, "pn2_ball_query: bad sizes B=%d N1=%lld N2=%lld K=%d", B,
               (long long)N1, (long long)N2, K);
   const int64_t total = (int64_t)B * N1;
@@ -406,7 +430,7 @@ int ball_query_entry(const T* query, const T* key, int B, int64_t N1, int64_t N2
   const T r = (T)radius;                              // ball_query_kernel.cu:45,73
   const T r2 = r * r;
   hipLaunchKernelGGL(ball_query_k<T>, dim3((unsigned)cdiv64(total, BQ_T / 64)), dim3(BQ_T), 0, (hipStream_t)stream, query,
-                     key, total, N1, N2, r2, K, index, distance);
+                     key, lengths, total, N1, N2, r2, K, index, distance);
   MVK_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -453,20 +477,44 @@ extern "C" int64_t mvk_fps_workspace(int64_t B, int64_t N, int f64) {
 
 extern "C" int mvk_fps(const float* points, int B, int64_t N, int D, int64_t M, int64_t* index, void* workspace,
                        int64_t workspace_bytes, void* stream) {
-  return fps_entry<float>(points, B, N, D, M, index, workspace, workspace_bytes, stream);
+  return fps_entry<float>(points, nullptr, B, N, D, M, index, workspace, workspace_bytes, stream);
 }
 extern "C" int mvk_fps_f64(const double* points, int B, int64_t N, int D, int64_t M, int64_t* index, void* workspace,
                            int64_t workspace_bytes, void* stream) {
-  return fps_entry<double>(points, B, N, D, M, index, workspace, workspace_bytes, stream);
+  return fps_entry<double>(points, nullptr, B, N, D, M, index, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mvk_fps_ragged(const float* points, const int64_t* lengths, int B, int64_t N, int D, int64_t M,
+                              int64_t* index, void* workspace, int64_t workspace_bytes, void* stream) {
+  MVK_REQUIRE(lengths || B <= 0, "fps_ragged: null lengths");
+  return fps_entry<float>(points, lengths, B, N, D, M, index, workspace, workspace_bytes, stream);
+}
+extern "C" int mvk_fps_ragged_f64(const double* points, const int64_t* lengths, int B, int64_t N, int D, int64_t M,
+                                  int64_t* index, void* workspace, int64_t workspace_bytes, void* stream) {
+  MVK_REQUIRE(lengths || B <= 0, "fps_ragged: null lengths");
+  return fps_entry<double>(points, lengths, B, N, D, M, index, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mvk_pn2_ball_query(const float* query, const float* key, int B, int64_t N1, int64_t N2, float radius, int K,
                                   int64_t* index, float* distance, void* stream) {
-  return ball_query_entry<float>(query, key, B, N1, N2, radius, K, index, distance, stream);
+  return ball_query_entry<float>(query, key, nullptr, B, N1, N2, radius, K, index, distance, stream);
 }
 extern "C" int mvk_pn2_ball_query_f64(const double* query, const double* key, int B, int64_t N1, int64_t N2, float radius,
                                       int K, int64_t* index, double* distance, void* stream) {
-  return ball_query_entry<double>(query, key, B, N1, N2, radius, K, index, distance, stream);
+  return ball_query_entry<double>(query, key, nullptr, B, N1, N2, radius, K, index, distance, stream);
+}
+
+extern "C" int mvk_pn2_ball_query_ragged(const float* query, const float* key, const int64_t* key_lengths, int B,
+                                         int64_t N1, int64_t N2, float radius, int K, int64_t* index, float* distance,
+                                         void* stream) {
+  MVK_REQUIRE(key_lengths || B <= 0 || N1 <= 0, "pn2_ball_query_ragged: null key_lengths");
+  return ball_query_entry<float>(query, key, key_lengths, B, N1, N2, radius, K, index, distance, stream);
+}
+extern "C" int mvk_pn2_ball_query_ragged_f64(const double* query, const double* key, const int64_t* key_lengths, int B,
+                                             int64_t N1, int64_t N2, float radius, int K, int64_t* index,
+                                             double* distance, void* stream) {
+  MVK_REQUIRE(key_lengths || B <= 0 || N1 <= 0, "pn2_ball_query_ragged: null key_lengths");
+  return ball_query_entry<double>(query, key, key_lengths, B, N1, N2, radius, K, index, distance, stream);
 }
 
 extern "C" int mvk_knn_distance(const float* query, const float* key, int B, int64_t N1, int64_t N2, int k, int64_t* index,

@@ -109,7 +109,9 @@ class MVPNet3D(nn.Module):
 
     def forward(self, data_batch):
         """images (b,nv,3,h,w), image_xyz (b,nv,h,w,3), knn_indices (b,np,k) int64 flat pixel indices
-        view*h*w + row*w + col, points (b,3,np) -> the 3D network's predictions."""
+        view*h*w + row*w + col, points (b,3,np) -> the 3D network's predictions. An optional 'lengths' (b,) int64 goes
+        through to net_3d (PN2SSG.forward: a padded batch at inference); the padded rows of knn_indices must be valid
+        pixel indices (0 will do), and the logit columns >= lengths[b] of batch element b are unspecified."""
         images = data_batch['images']
         b, nv, _, h, w = images.size()
         feature_2d = self.net_2d({'image': images.reshape([-1] + list(images.shape[2:]))})['feature']
@@ -121,7 +123,10 @@ class MVPNet3D(nn.Module):
             image_xyz = ops.group_points(image_xyz, knn_indices)                   # (b, 3, np, k)
         points = data_batch['points']
         feature_2d3d = self.feat_aggreg(image_xyz, points, feature_2d)             # (b, out, np)
-        return self.net_3d({'points': points, 'feature': feature_2d3d})
+        batch_3d = {'points': points, 'feature': feature_2d3d}
+        if data_batch.get('lengths', None) is not None:
+            batch_3d['lengths'] = data_batch['lengths']
+        return self.net_3d(batch_3d)
 
     def get_loss(self, cfg):
         from mvpnet.models.loss import SegLoss

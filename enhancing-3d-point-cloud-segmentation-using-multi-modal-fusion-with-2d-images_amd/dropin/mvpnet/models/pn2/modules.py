@@ -126,10 +126,11 @@ class QueryGrouper(nn.Module):
         self.radius = radius
         self.max_neighbors = max_neighbors
 
-    def forward(self, new_xyz, xyz, feature, use_xyz):
-        """new_xyz (B,3,M), xyz (B,3,N), feature (B,C,N) or None -> group_feature (B,C[+3],M,K), group_xyz (B,3,M,K)."""
+    def forward(self, new_xyz, xyz, feature, use_xyz, key_lengths=None):
+        """new_xyz (B,3,M), xyz (B,3,N), feature (B,C,N) or None -> group_feature (B,C[+3],M,K), group_xyz (B,3,M,K).
+        key_lengths: (B,) int64 or None; only the first key_lengths[b] columns of xyz[b] are searched."""
         with torch.no_grad():
-            index = ball_query(new_xyz, xyz, self.radius, self.max_neighbors)
+            index = ball_query(new_xyz, xyz, self.radius, self.max_neighbors, key_lengths=key_lengths)
         group_xyz = group_points(xyz, index) - new_xyz.unsqueeze(-1)
         if feature is None:
             return group_xyz, group_xyz
@@ -159,15 +160,20 @@ class SetAbstraction(Freezable, nn.Module):
         self.mlp = SharedMLP(self.in_channels, mlp_channels, ndim=2, bn=True)
         self.grouper = None if num_centroids == 0 else QueryGrouper(radius, max_neighbors)
 
-    def forward(self, xyz, feature=None):
-        """xyz (B,3,N), feature (B,C,N) or None -> new_xyz (B,3,M), new_feature (B,out_channels,M)."""
+    def forward(self, xyz, feature=None, lengths=None):
+        """xyz (B,3,N), feature (B,C,N) or None -> new_xyz (B,3,M), new_feature (B,out_channels,M). lengths: (B,) int64
+        on xyz's device or None, for a padded batch (inference): cloud b is its first lengths[b] columns, centroids
+        and neighbours are those of that cloud alone, and all M output columns are valid. It needs num_centroids > 0
+        (with 0 or -1 the padding would reach the output)."""
+        if lengths is not None and self.num_centroids <= 0:
+            raise ValueError('SetAbstraction: lengths needs num_centroids > 0, got {}'.format(self.num_centroids))
         frozen = self._use_frozen(xyz, feature)
         if frozen is not None:
             if self.num_centroids == -1:
                 new_xyz = xyz
             else:
-                new_xyz = batch_index_select(xyz, farthest_point_sample(xyz, self.num_centroids), dim=2)
-            index = ball_query(new_xyz, xyz, self.radius, self.max_neighbors)
+                new_xyz = batch_index_select(xyz, farthest_point_sample(xyz, self.num_centroids, lengths=lengths), dim=2)
+            index = ball_query(new_xyz, xyz, self.radius, self.max_neighbors, key_lengths=lengths)
             return new_xyz, ops.pn2_sa_mlp_max(xyz.contiguous(), None if feature is None else feature.contiguous(),
                                                new_xyz.contiguous(), index, *frozen)
         if self.num_centroids == 0:
@@ -181,9 +187,9 @@ class SetAbstraction(Freezable, nn.Module):
                 new_xyz = xyz
             else:
                 with torch.no_grad():
-                    index = farthest_point_sample(xyz, self.num_centroids)
+                    index = farthest_point_sample(xyz, self.num_centroids, lengths=lengths)
                 new_xyz = batch_index_select(xyz, index, dim=2)
-            group_feature, _ = self.grouper(new_xyz, xyz, feature, use_xyz=self.use_xyz)
+            group_feature, _ = self.grouper(new_xyz, xyz, feature, use_xyz=self.use_xyz, key_lengths=lengths)
         new_feature = self.mlp(group_feature)
         return new_xyz, torch.max(new_feature, dim=3)[0]
 

@@ -60,12 +60,25 @@ class PN2SSG(Freezable, nn.Module):
         self.reset_parameters()
 
     def forward(self, data_batch):
-        """data_batch['points'] (B,3,N), optional data_batch['feature'] (B,C,N) -> {'seg_logit': (B,num_classes,N)}."""
+        """data_batch['points'] (B,3,N), optional data_batch['feature'] (B,C,N) -> {'seg_logit': (B,num_classes,N)}.
+        Optional data_batch['lengths'] (B,) int64 on the points' device, inference only: a padded batch of clouds of
+        different sizes. Cloud b is the first lengths[b] columns; the first set abstraction samples and groups within
+        them, so the logit columns [0, lengths[b]) of batch element b are those of a forward of that cloud alone. The
+        logit columns >= lengths[b] are unspecified. Raises ValueError when the first set abstraction has
+        num_centroids <= 0 (the next level would be ragged) and RuntimeError in training mode (batch statistics would
+        include the padded columns)."""
         xyz = data_batch['points']
         feature = data_batch.get('feature', None)
+        lengths = data_batch.get('lengths', None)
+        if lengths is not None:
+            if self.sa_modules[0].num_centroids <= 0:
+                raise ValueError('PN2SSG: lengths needs num_centroids[0] > 0, got {}'.format(
+                    self.sa_modules[0].num_centroids))
+            if self.training:
+                raise RuntimeError('PN2SSG: lengths is for inference; call eval() first')
         xyzs, feats = [xyz], [None]
-        for sa in self.sa_modules:
-            xyz, feature = sa(xyz, feature)
+        for lv, sa in enumerate(self.sa_modules):
+            xyz, feature = sa(xyz, feature) if lv > 0 or lengths is None else sa(xyz, feature, lengths=lengths)
             xyzs.append(xyz)
             feats.append(feature)
         up = feats[-1]

@@ -2216,33 +2216,65 @@ def _pn2_float(name, *ts):
     return [t.detach().contiguous() for t in ts], dt == torch.float64
 
 
-def fps(points, num_centroids):
+def _pn2_lengths(name, lengths, points):
+    """The per-cloud point counts of a ragged point op: an int64 tensor (B,) on the device of `points` (B,N,D). Anything
+    else is refused; the value and its form are checked before the device."""
+    if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int64:
+        raise RuntimeError("%s: lengths must be an int64 tensor, got %s"
+                           % (name, lengths.dtype if isinstance(lengths, torch.Tensor) else type(lengths).__name__))
+    if lengths.dim() != 1 or lengths.shape[0] != points.shape[0]:
+        raise RuntimeError("%s: lengths must have shape (%d,), one count per cloud, got %s"
+                           % (name, points.shape[0], tuple(lengths.shape)))
+    _dev(lengths)
+    if lengths.device != points.device:
+        raise RuntimeError("%s: lengths on %s, points on %s" % (name, lengths.device, points.device))
+    return lengths.detach().contiguous()
+
+
+def fps(points, num_centroids, lengths=None):
     """Farthest point sampling: points (B,N,D) with D in {2,3} -> int64 (B,num_centroids), the reference's picks
-    including its order among ties (mvpnet/ops/cuda/fps_kernel.cu:60-135)."""
-    (pts,), f64 = _pn2_float("fps", points)
-    if pts.dim() != 3:
+    including its order among ties (mvpnet/ops/cuda/fps_kernel.cu:60-135). lengths: int64 (B,) on the points' device,
+    for a padded batch: cloud b is points[b, :lengths[b]] (clamped to [1, N]), the rows behind it are never read, and
+    row b of the result is what fps(points[b:b+1, :lengths[b]]) returns, the last pick repeated where num_centroids
+    exceeds lengths[b] and no point is left at a positive distance."""
+    if points.dim() != 3:
         raise RuntimeError("fps: expected points (B,N,D)")
+    if lengths is not None:
+        lengths = _pn2_lengths("fps", lengths, points)
+    (pts,), f64 = _pn2_float("fps", points)
     B, N, D = pts.shape
     M = int(num_centroids)
     out = torch.empty((B, M if M > 0 else 0), device=pts.device, dtype=torch.int64)
     nbytes = lib().mvk_fps_workspace(B, N, int(f64))
     ws = torch.empty((nbytes,), device=pts.device, dtype=torch.uint8) if nbytes > 0 else None
+    if lengths is not None:
+        fn = lib().mvk_fps_ragged_f64 if f64 else lib().mvk_fps_ragged
+        check(fn(_p(pts), _p(lengths), B, N, D, M, _p(out), _p(ws), nbytes, _stream()))
+        return out
     fn = lib().mvk_fps_f64 if f64 else lib().mvk_fps
     check(fn(_p(pts), B, N, D, M, _p(out), _p(ws), nbytes, _stream()))
     return out
 
 
-def pn2_ball_query(query, key, radius, max_neighbors, with_distance=False):
+def pn2_ball_query(query, key, radius, max_neighbors, with_distance=False, key_lengths=None):
     """query (B,N1,3), key (B,N2,3) -> int64 (B,N1,K): the first K keys in index order with d2 < radius^2, padded with
     the first hit, -1 where there is none (ball_query_kernel.cu:59-135). with_distance: also d2 (B,N1,K), -1 in padded
-    slots (ball_query_distance_kernel.cu)."""
-    (q, k), f64 = _pn2_float("pn2_ball_query", query, key)
-    if q.dim() != 3 or k.dim() != 3 or q.shape[2] != 3 or k.shape[2] != 3 or q.shape[0] != k.shape[0]:
+    slots (ball_query_distance_kernel.cu). key_lengths: int64 (B,) on the keys' device, for a padded batch: the keys of
+    batch element b are key[b, :key_lengths[b]] (clamped to [1, N2]); every query is answered."""
+    if query.dim() != 3 or key.dim() != 3 or query.shape[2] != 3 or key.shape[2] != 3 \
+            or query.shape[0] != key.shape[0]:
         raise RuntimeError("pn2_ball_query: expected query (B,N1,3) and key (B,N2,3)")
+    if key_lengths is not None:
+        key_lengths = _pn2_lengths("pn2_ball_query", key_lengths, key)
+    (q, k), f64 = _pn2_float("pn2_ball_query", query, key)
     B, N1, _ = q.shape
     N2, K = k.shape[1], int(max_neighbors)
     index = torch.empty((B, N1, max(K, 0)), device=q.device, dtype=torch.int64)
     dist = torch.empty((B, N1, max(K, 0)), device=q.device, dtype=q.dtype) if with_distance else None
+    if key_lengths is not None:
+        fn = lib().mvk_pn2_ball_query_ragged_f64 if f64 else lib().mvk_pn2_ball_query_ragged
+        check(fn(_p(q), _p(k), _p(key_lengths), B, N1, N2, float(radius), K, _p(index), _p(dist), _stream()))
+        return (index, dist) if with_distance else index
     fn = lib().mvk_pn2_ball_query_f64 if f64 else lib().mvk_pn2_ball_query
     check(fn(_p(q), _p(k), B, N1, N2, float(radius), K, _p(index), _p(dist), _stream()))
     return (index, dist) if with_distance else index

@@ -699,6 +699,22 @@ int mvk_pn2_ball_query(const float* query, const float* key, int B, int64_t N1, 
                        int64_t* index, float* distance, void* stream);
 int mvk_pn2_ball_query_f64(const double* query, const double* key, int B, int64_t N1, int64_t N2, float radius, int K,
                            int64_t* index, double* distance, void* stream);
+/* The ragged forms of the two above, for a padded batch of clouds of different sizes (inference). `lengths`
+ * / `key_lengths`: int64 [B] on the device, not NULL; a value outside [1, N] is clamped into it by the kernel. Nothing is
+ * read back: the entry points stay capturable.
+ * mvk_fps_ragged: cloud b is the rows [0, lengths[b]) of points[b]; rows at or beyond it are never read (they may hold
+ * NaN). index[b] is what mvk_fps picks on that cloud alone, ties included; where M exceeds lengths[b] the last pick
+ * repeats once no point has a positive distance. 1 <= M <= N; threads, registers and workspace are sized by N.
+ * mvk_pn2_ball_query_ragged: the keys of batch element b are the rows [0, key_lengths[b]) of key[b]; all N1 queries are
+ * answered, and every index is below key_lengths[b] (or -1). */
+int mvk_fps_ragged(const float* points, const int64_t* lengths, int B, int64_t N, int D, int64_t M, int64_t* index,
+                   void* workspace, int64_t workspace_bytes, void* stream);
+int mvk_fps_ragged_f64(const double* points, const int64_t* lengths, int B, int64_t N, int D, int64_t M, int64_t* index,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+int mvk_pn2_ball_query_ragged(const float* query, const float* key, const int64_t* key_lengths, int B, int64_t N1,
+                              int64_t N2, float radius, int K, int64_t* index, float* distance, void* stream);
+int mvk_pn2_ball_query_ragged_f64(const double* query, const double* key, const int64_t* key_lengths, int B, int64_t N1,
+                                  int64_t N2, float radius, int K, int64_t* index, double* distance, void* stream);
 /* 3-NN (knn_distance_kernel.cu:35-124): k must be 3 and N2 >= 3. index [B,N1,3] and SQUARED distance [B,N1,3] in the
  * input dtype, ascending by distance; of two keys at the same distance the lower index comes first. */
 int mvk_knn_distance(const float* query, const float* key, int B, int64_t N1, int64_t N2, int k, int64_t* index,
