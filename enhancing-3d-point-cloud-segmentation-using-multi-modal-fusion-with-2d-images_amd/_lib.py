@@ -183,6 +183,8 @@ _SIGNATURES = {
     "mvk_pn2_mlp_supported": (C.c_int, [_vp, _i]),
     "mvk_pn2_sa_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _vp, _vp]),
     "mvk_pn2_fp_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _vp]),
+    "mvk_pn2_fa_fwd": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _i, _i,
+                                 _vp, _vp]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -2,7 +2,9 @@
 // and a FeaturePropagation's "interpolate, concatenate, shared MLP" as one launch each. The grouped (B,C,M,K) tensor and
 // the activations between the layers never leave the workgroup: a tile of R rows (neighbours of some centroids, or dense
 // points) is staged into LDS, up to three layers y = relu(W x + b) run on it with v_mfma_f32_16x16x4_f32 (exact f32, a
-// k-ordered fma chain per output), ping-ponging between two LDS buffers, and only the result goes to HBM.
+// k-ordered fma chain per output), ping-ponging between two LDS buffers, and only the result goes to HBM. A third front
+// end on the same core is MVPNet3D's FeatureAggregation fed from the 2D encoder's map: gather by flat pixel
+// index, relation channels, shared MLP, sum or max over the neighbours.
 //
 // Contraction: this file is compiled with -ffp-contract=off (build.py), like pn2.hip. The layers lose nothing by it: their
 // products are MFMA builtins, which the flag does not touch, and the staging is loads and one subtraction. The one piece
@@ -247,11 +249,106 @@ __global__ __launch_bounds__(MT) void pn2_fp_k(const float* __restrict__ sparse,
   }
 }
 
+// Feature aggregation. Grid (ceil(N / G), B); the tile holds all K rows of G = R / K points, one pass. Row
+// (n, k) with j = index[b, n, k]: [feat(image j / HW, c, pixel j % HW) for c < C | diff_0..2 | dist], diff_d =
+// image_xyz[b, j, d] - points[b, d, n], dist = (diff_0^2 + diff_1^2) + diff_2^2; j outside [0, P) reads as zero for the
+// features and for image_xyz BEFORE the subtraction. feat is addressed through element strides (image, channel,
+// pixel): an NCHW map puts lanes along the rows (each lane's read stays in one channel plane, like group_points), a
+// channels-last map (sc == 1) puts 16 lanes along the channels of one row. The reduction over k (sum in ascending k
+// from the k = 0 value, or fmaxf) reads the last layer's outputs from LDS with lanes along the points. Cloud b is its
+// first nb = clamp(lengths[b], 1, N) columns: the columns behind are stored as zeros and their indices never read.
+__global__ __launch_bounds__(MT) void pn2_fa_k(const float* __restrict__ feat, int64_t si, int64_t sc, int64_t sp,
+                                               const float* __restrict__ image_xyz, const float* __restrict__ points,
+                                               const int64_t* __restrict__ index, const int64_t* __restrict__ lengths,
+                                               const float* __restrict__ params, Chain ch, int C, int nv, int HW, int64_t N,
+                                               int K, int rshift, int G, int reduce, float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int R = 1 << rshift, t = threadIdx.x;
+  float* buf0 = lds;
+  float* buf1 = buf0 + R * ch.stride[0];
+  int64_t* roff = reinterpret_cast<int64_t*>(buf1 + R * ch.stride[1]);   // image * si + pixel * sp of the row's pixel
+  int* ridx = reinterpret_cast<int*>(roff + R);                          // key of the row: >= 0, -1 outside [0, P), -2 no row
+  int* rcen = ridx + R;                                                  // point of the row, relative to n0
+  const int64_t b = blockIdx.y, n0 = (int64_t)blockIdx.x * G, P = (int64_t)nv * HW;
+  int64_t nb = N;
+  if (lengths) {
+    nb = lengths[b];
+    nb = nb < 1 ? 1 : (nb > N ? N : nb);
+  }
+  const int cols = (int)(N - n0 < G ? N - n0 : G);                       // columns of `out` this workgroup owns
+  const int gcnt = nb - n0 >= cols ? cols : (nb > n0 ? (int)(nb - n0) : 0);   // of which valid
+  const int Cin = ch.width[0], kpad = pad16(Cin), Cout = ch.width[ch.n_layers];
+  for (int e = t; e < (cols - gcnt) * Cout; e += MT) {
+    const int g = gcnt + e % (cols - gcnt), c = e / (cols - gcnt);
+    out[(b * Cout + c) * N + n0 + g] = 0.0f;
+  }
+  if (gcnt == 0) return;
+  const int rows = gcnt * K;
+  for (int r = t; r < R; r += MT) {
+    int v = -2, g = 0;
+    int64_t off = 0;
+    if (r < rows) {
+      g = r / K;
+      const int64_t j = index[(b * N + n0 + g) * K + (r - g * K)];
+      v = -1;
+      if (j >= 0 && j < P) {
+        v = (int)j;
+        const int img = v / HW;
+        off = img * si + (v - img * HW) * sp;
+      }
+    }
+    roff[r] = off;
+    ridx[r] = v;
+    rcen[r] = g;
+  }
+  __syncthreads();
+  const float* fb = feat + b * nv * si;
+  const float* xb = image_xyz + b * P * 3;
+  const float* pb = points + b * 3 * N + n0;
+  const bool along_c = sc == 1 && C > 1;
+  for (int e = t; e < (kpad << rshift); e += MT) {
+    const int r = along_c ? (e >> 4) & (R - 1) : e & (R - 1);
+    const int c = along_c ? (e & 15) + ((e >> (4 + rshift)) << 4) : e >> rshift;
+    const int j = ridx[r];
+    float v = 0.0f;
+    if (j != -2 && c < Cin) {
+      if (c < C) {
+        v = j >= 0 ? fb[roff[r] + c * sc] : 0.0f;
+      } else {
+        const int d = c - C, g = rcen[r];
+        if (d < 3) {
+          v = (j >= 0 ? xb[(int64_t)j * 3 + d] : 0.0f) - pb[d * N + g];
+        } else {
+          const float d0 = (j >= 0 ? xb[(int64_t)j * 3] : 0.0f) - pb[g];
+          const float d1 = (j >= 0 ? xb[(int64_t)j * 3 + 1] : 0.0f) - pb[N + g];
+          const float d2 = (j >= 0 ? xb[(int64_t)j * 3 + 2] : 0.0f) - pb[2 * N + g];
+          v = (d0 * d0 + d1 * d1) + d2 * d2;
+        }
+      }
+    }
+    buf0[r * ch.stride[0] + c] = v;
+  }
+  __syncthreads();
+  int sf;
+  const float* y = mlp_chain(ch, params, buf0, buf1, R, &sf);
+  for (int e = t; e < gcnt * Cout; e += MT) {
+    const int g = e % gcnt, c = e / gcnt;
+    const float* col = y + g * K * sf + c;
+    float acc = col[0];
+    if (reduce) {
+      for (int k = 1; k < K; ++k) acc = fmaxf(acc, col[k * sf]);
+    } else {
+      for (int k = 1; k < K; ++k) acc = acc + col[k * sf];
+    }
+    out[(b * Cout + c) * N + n0 + g] = acc;
+  }
+}
+
 // Bytes of LDS of a tile of R rows: the two activation buffers and `aux` words per row of the front end's own.
 inline int64_t lds_bytes(const Chain& ch, int R, int aux) {
   return (int64_t)R * (ch.stride[0] + ch.stride[1] + aux) * 4;
 }
-constexpr int AUX_SA = 2, AUX_FP = 6, AUX_MAX = 6;
+constexpr int AUX_SA = 2, AUX_FP = 6, AUX_FA = 4, AUX_MAX = 6;
 
 // Widths, offsets and LDS strides of a chain, and the one statement of what is supported. Returns 0, or -1 with the
 // error set.
@@ -353,6 +450,36 @@ extern "C" int mvk_pn2_fp_fwd(const float* sparse_feature, const int64_t* index,
   if (allow_lds(pn2_fp_k, lds)) return -2;
   hipLaunchKernelGGL(pn2_fp_k, dim3((unsigned)gx, (unsigned)B), dim3(MT), (size_t)lds, (hipStream_t)stream, sparse_feature,
                      index, weight, dense_feature, params, ch, C2, C1, N2, N1, rs, out, status);
+  MVK_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int mvk_pn2_fa_fwd(const float* feature_2d, int64_t stride_image, int64_t stride_channel, int64_t stride_pixel,
+                              const float* image_xyz, const float* points, const int64_t* index, const int64_t* lengths,
+                              const float* params, const int* widths_host, int n_layers, int B, int nv, int C, int64_t HW,
+                              int64_t N, int K, int use_relation, int reduce, float* out, void* stream) {
+  Chain ch;
+  if (make_chain("pn2_fa_fwd", params, widths_host, n_layers, 1, &ch)) return -1;
+  MVK_REQUIRE(K >= 1 && K <= 128, "pn2_fa_fwd: K = %d neighbours (1 .. 128 are supported)", K);
+  MVK_REQUIRE(B >= 0 && B < 65536 && nv >= 1 && C >= 1 && HW >= 1 && N >= 0 && N < ((int64_t)1 << 31) &&
+                  (int64_t)nv * HW < ((int64_t)1 << 31),
+              "pn2_fa_fwd: bad sizes B=%d nv=%d C=%d HW=%lld N=%lld", B, nv, C, (long long)HW, (long long)N);
+  MVK_REQUIRE(reduce == 0 || reduce == 1, "pn2_fa_fwd: reduce = %d (0 sum, 1 max)", reduce);
+  MVK_REQUIRE(ch.width[0] == C + (use_relation ? 4 : 0), "pn2_fa_fwd: widths[0] = %d, the input rows hold %d values",
+              ch.width[0], C + (use_relation ? 4 : 0));
+  const int rs = pick_rshift(ch, AUX_FA, (int64_t)B * N * K, K);
+  const int R = 1 << rs;
+  MVK_REQUIRE(K <= R, "pn2_fa_fwd: widths %d, %d, %d, %d leave no room in LDS for a tile of K = %d rows", ch.width[0],
+              ch.width[1], ch.width[2], ch.width[3], K);
+  if (B == 0 || N == 0) return 0;
+  MVK_REQUIRE(feature_2d && image_xyz && points && index && params && out, "pn2_fa_fwd: null operand");
+  const int G = R / K;
+  const int64_t gx = cdiv64(N, G), lds = lds_bytes(ch, R, AUX_FA);
+  MVK_REQUIRE(gx < ((int64_t)1 << 31), "pn2_fa_fwd: too many points");
+  if (allow_lds(pn2_fa_k, lds)) return -2;
+  hipLaunchKernelGGL(pn2_fa_k, dim3((unsigned)gx, (unsigned)B), dim3(MT), (size_t)lds, (hipStream_t)stream, feature_2d,
+                     stride_image, stride_channel, stride_pixel, image_xyz, points, index, lengths, params, ch, C, nv, (int)HW,
+                     N, K, rs, G, reduce, out);
   MVK_CHECK_HIP(hipGetLastError());
   return 0;
 }

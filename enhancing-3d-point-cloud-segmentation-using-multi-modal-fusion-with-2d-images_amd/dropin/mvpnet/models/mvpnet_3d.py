@@ -2,7 +2,9 @@
 [feat_2d | dxyz | |dxyz|^2] -> SharedMLP (1x1 conv + BN + ReLU) -> reduction over k.
 Sub-module names (mlp.{i}.conv / mlp.{i}.bn) match the reference so MVPNet checkpoints load.
 MVPNet3D (reference :73-135): the baseline's wiring 2D encoder -> unprojection by group_points ->
-FeatureAggregation -> 3D network (PN2SSG)."""
+FeatureAggregation -> 3D network (PN2SSG). After freeze_inference(net, aggregation=True) (pn2/modules.py) the
+unprojection and the aggregation of an eval-mode forward under torch.no_grad() are ONE fused launch on the encoder's
+map (ops.pn2_fa_mlp, csrc/pn2_mlp.hip)."""
 import logging
 
 import numpy as np
@@ -16,10 +18,14 @@ try:
 except ImportError:
     from common.nn import SharedMLP, xavier_uniform
     from _native import ops
+from .pn2.modules import Freezable, fold_chain
 
 
-class FeatureAggregation(nn.Module):
-    """Feature Aggregation inspired by ContFuse"""
+class FeatureAggregation(Freezable, nn.Module):
+    """Feature Aggregation inspired by ContFuse. After freeze_inference(net, aggregation=True) it holds a snapshot
+    (params, widths, reduction name, use_relation) -- a plain attribute, no state-dict key, dropped by train(True) --
+    and from_encoder_map runs the whole module, grouping included, as one fused launch."""
+    _freeze_on_request = True
 
     def __init__(self, in_channels, mlp_channels=(64, 64, 64), reduction='sum', use_relation=True):
         super(FeatureAggregation, self).__init__()
@@ -35,7 +41,27 @@ class FeatureAggregation(nn.Module):
             self.reduction = torch.sum
         elif reduction == 'max':
             self.reduction = lambda x, dim: torch.max(x, dim)[0]
+        self._reduction_name = reduction if reduction in ('sum', 'max') else None
         self.reset_parameters()
+
+    def _snapshot(self):
+        """fold_chain of the shared MLP plus the two flags, or None where the fused kernel does not apply: no MLP,
+        more than three layers, unsupported widths."""
+        if self.mlp is None or self._reduction_name is None:
+            return None
+        chain = fold_chain(self.mlp)
+        return None if chain is None else chain + (self._reduction_name, bool(self.use_relation))
+
+    def from_encoder_map(self, frozen, feature_2d, image_xyz, knn_indices, points, lengths=None):
+        """The frozen module on the encoder's output as it lies: feature_2d (b*nv,c,h,w) contiguous or channels-last,
+        image_xyz (b,nv,h,w,3), knn_indices (b,np,k) int64 flat pixel indices, points (b,3,np) -> (b,out,np), what
+        forward() gives on the two group_points results. frozen: the snapshot _use_frozen returned. One launch
+        (ops.pn2_fa_mlp); columns >= lengths[b] come out as zeros."""
+        params, widths, reduction, use_relation = frozen
+        if not (feature_2d.is_contiguous() or feature_2d.is_contiguous(memory_format=torch.channels_last)):
+            feature_2d = feature_2d.contiguous()
+        return ops.pn2_fa_mlp(feature_2d, image_xyz.contiguous(), points.contiguous(), knn_indices.contiguous(), params,
+                              widths, reduction=reduction, use_relation=use_relation, lengths=lengths)
 
     def forward(self, src_xyz, tgt_xyz, feature):
         """src_xyz (b,3,np,k), tgt_xyz (b,3,np), feature (b,c,np,k) -> (b,out,np)."""
@@ -116,6 +142,17 @@ class MVPNet3D(nn.Module):
         b, nv, _, h, w = images.size()
         feature_2d = self.net_2d({'image': images.reshape([-1] + list(images.shape[2:]))})['feature']
         knn_indices = data_batch['knn_indices']
+        frozen = self.feat_aggreg._use_frozen(feature_2d, data_batch['image_xyz'], data_batch['points'])
+        if frozen is not None and not self.training and knn_indices.shape[2] <= 128:
+            # the 2D -> 3D hand-off as one launch on the encoder's map (freeze_inference(net, aggregation=True))
+            points = data_batch['points']
+            lengths = data_batch.get('lengths', None)
+            batch_3d = {'points': points,
+                        'feature': self.feat_aggreg.from_encoder_map(frozen, feature_2d, data_batch['image_xyz'],
+                                                                     knn_indices, points, lengths=lengths)}
+            if lengths is not None:
+                batch_3d['lengths'] = lengths
+            return self.net_3d(batch_3d)
         feature_2d = feature_2d.reshape(b, nv, -1, h, w).transpose(1, 2).contiguous().reshape(b, -1, nv * h * w)
         feature_2d = ops.group_points(feature_2d, knn_indices)                     # (b, c, np, k)
         with torch.no_grad():

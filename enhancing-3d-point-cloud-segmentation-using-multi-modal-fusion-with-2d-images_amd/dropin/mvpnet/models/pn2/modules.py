@@ -65,8 +65,10 @@ def fold_chain(layers, head=None):
 
 class Freezable(object):
     """A module with a frozen inference path. _frozen is a plain attribute (no state-dict key): None, or the snapshot
-    that _snapshot() took. train(True) drops it."""
+    that _snapshot() took. train(True) drops it. _freeze_on_request: freeze_inference snapshots the module only when
+    asked to by name (FeatureAggregation: aggregation=True)."""
     _frozen = None
+    _freeze_on_request = False
 
     def _snapshot(self):
         raise NotImplementedError
@@ -87,7 +89,7 @@ class Freezable(object):
         return super(Freezable, self).train(mode)
 
 
-def freeze_inference(net):
+def freeze_inference(net, aggregation=False):
     """Snapshot, for inference, the shared MLPs of every SetAbstraction, FeaturePropagation and PN2SSG under `net` (an
     MVPNet3D is reached through its net_3d): BatchNorm's running statistics folded into the 1x1 convolutions in
     float64, packed as float32 (fold_chain). In eval mode under torch.no_grad() a SetAbstraction with centroids is then
@@ -101,10 +103,15 @@ def freeze_inference(net):
     The snapshot is a plain attribute, not a buffer: state-dict keys stay as they are. It is a copy: after
     load_state_dict (or any other change of the parameters or running statistics, or a move to another device) call
     freeze_inference again. train(True) on a module drops its snapshot; unfreeze_inference drops all of them.
-    Returns net."""
+
+    aggregation=True additionally snapshots every FeatureAggregation under `net` (an MVPNet3D's feat_aggreg): its
+    shared MLP folded the same way, plus the reduction and relation flags. MVPNet3D.forward then goes from the 2D
+    encoder's map to the 3D network's input features in ONE ops.pn2_fa_mlp launch -- no transposed copy of the map, no
+    group_points, no concatenation, no Conv2d / BatchNorm2d forward -- under the same conditions (eval mode, gradients
+    off, float32). The default leaves FeatureAggregation modules exactly as they are. Returns net."""
     with torch.no_grad():
         for m in net.modules():
-            if isinstance(m, Freezable):
+            if isinstance(m, Freezable) and (aggregation or not m._freeze_on_request):
                 m._frozen = m._snapshot()
     return net
 

@@ -2476,6 +2476,51 @@ def pn2_fp_mlp(sparse, index, weight, dense, params, widths, relu_last=True):
     return out
 
 
+def pn2_fa_mlp(feature_2d, image_xyz, points, index, params, widths, reduction='sum', use_relation=True, lengths=None):
+    """A frozen FeatureAggregation fed from the 2D encoder's map, as one launch: feature_2d (B*nv,C,h,w), contiguous or
+    channels-last and read in place, image_xyz (B,nv,h,w,3), points (B,3,N), index (B,N,K) int64 flat pixel indices
+    view*h*w + pixel -> (B,widths[-1],N), the sum (or max) over k of the chain applied to the row [feature_2d at the
+    pixel | image_xyz at the pixel - point | squared distance]; the features alone with use_relation False. An index
+    outside [0, nv*h*w) reads as zero before the point is subtracted, like group_points. lengths: int64 (B,) on the
+    device, for a padded batch: columns >= lengths[b] (clamped to [1, N]) of element b come out as zeros, and their
+    indices and points are never read. K <= 128. params, widths and the rest as pn2_sa_mlp_max."""
+    name = "pn2_fa_mlp"
+    if feature_2d.dtype != torch.float32:
+        raise RuntimeError("%s: floating operands must be float32 (got %s)" % (name, feature_2d.dtype))
+    if feature_2d.dim() != 4:
+        raise RuntimeError("%s: expected feature_2d (B*nv,C,h,w)" % name)
+    channels_last = not feature_2d.is_contiguous()
+    if channels_last and not feature_2d.is_contiguous(memory_format=torch.channels_last):
+        raise RuntimeError("%s: feature_2d must be contiguous or channels-last" % name)
+    if feature_2d.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("%s has no backward: call it under torch.no_grad() or on detached tensors" % name)
+    if reduction not in ('sum', 'max'):
+        raise RuntimeError("%s: reduction must be 'sum' or 'max', got %r" % (name, reduction))
+    if image_xyz.dim() != 5 or image_xyz.shape[4] != 3 or points.dim() != 3 or points.shape[1] != 3 or index.dim() != 3 \
+            or points.shape[0] != image_xyz.shape[0] or tuple(index.shape[:2]) != (points.shape[0], points.shape[2]) \
+            or tuple(image_xyz.shape[2:4]) != tuple(feature_2d.shape[2:]):
+        raise RuntimeError("%s: expected feature_2d (B*nv,C,h,w), image_xyz (B,nv,h,w,3), points (B,3,N), index (B,N,K)"
+                           % name)
+    B, nv, h, w = image_xyz.shape[:4]
+    Cf, N, K = feature_2d.shape[1], points.shape[2], index.shape[2]
+    if feature_2d.shape[0] != B * nv:
+        raise RuntimeError("%s: feature_2d holds %d images, image_xyz has %d x %d views" % (name, feature_2d.shape[0], B, nv))
+    rows = Cf + (4 if use_relation else 0)
+    if len(widths) and int(widths[0]) != rows:
+        raise RuntimeError("%s: widths[0] = %d, the input rows hold %d values" % (name, int(widths[0]), rows))
+    if lengths is not None:
+        lengths = _pn2_lengths(name, lengths, points)
+    widths, w_host = _pn2_mlp_args(name, (image_xyz, points), index, params, widths)
+    _dev(feature_2d)
+    hw = h * w
+    strides = (Cf * hw, 1, Cf) if channels_last else (Cf * hw, hw, 1)
+    out = torch.empty((B, widths[-1], N), device=points.device, dtype=torch.float32)
+    check(lib().mvk_pn2_fa_fwd(_p(feature_2d), strides[0], strides[1], strides[2], _p(image_xyz), _p(points), _p(index),
+                               _p(lengths), _p(params), w_host, len(widths) - 1, B, nv, Cf, hw, N, K,
+                               int(bool(use_relation)), int(reduction == 'max'), _p(out), _stream()))
+    return out
+
+
 # --------------------------------------------------------------------------------------------
 # fused FeatureAggregation path: gather kernel + MFMA linear layers
 # --------------------------------------------------------------------------------------------

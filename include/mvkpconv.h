@@ -765,6 +765,22 @@ int mvk_pn2_sa_fwd(const float* xyz, const float* feature, const float* new_xyz,
 int mvk_pn2_fp_fwd(const float* sparse_feature, const int64_t* index, const float* weight, const float* dense_feature,
                    const float* params, const int* widths_host, int n_layers, int relu_last, int B, int C2, int C1,
                    int64_t N2, int64_t N1, float* out, int32_t* status, void* stream);
+/* Feature aggregation (MVPNet's 2D -> 3D hand-off), on the encoder's map as it lies: feature_2d holds B * nv images of C
+ * channels x HW pixels, element (image i, channel c, pixel p) at i * stride_image + c * stride_channel + p * stride_pixel
+ * (NCHW: C * HW, HW, 1; channels-last: C * HW, 1, C); image_xyz [B, nv * HW, 3]; points [B,3,N]; index [B,N,K] int64 flat
+ * pixel indices j = view * HW + pixel in [0, P), P = nv * HW; lengths int64 [B] on the device or NULL ->
+ * out [B,widths[n_layers],N] = the reduction over k (reduce 0: sum in ascending k in float32 from the k = 0 value;
+ * 1: fmaxf) of the chain applied to the row [feature_2d(b * nv + j / HW, c, j % HW) for c < C | diff_0..2 | dist],
+ * diff_d = image_xyz[b, j, d] - points[b, d, n], dist = (diff_0^2 + diff_1^2) + diff_2^2 with every operation rounded
+ * (torch.cat([feature, diff_xyz, distance])); use_relation == 0: the C features alone. An index outside [0, P) reads as
+ * zero for the features and for image_xyz BEFORE the subtraction, and the row takes part in the reduction. Cloud b is
+ * its first n_b = clamp(lengths[b], 1, N) columns (NULL: all N): columns >= n_b are written as zeros and their rows of
+ * index and columns of points are never read. An output depends on its own K rows only, in fixed order. 1 <= K <= 128,
+ * and the chain must leave room in LDS for a tile of K rows; P < 2^31. */
+int mvk_pn2_fa_fwd(const float* feature_2d, int64_t stride_image, int64_t stride_channel, int64_t stride_pixel,
+                   const float* image_xyz, const float* points, const int64_t* index, const int64_t* lengths,
+                   const float* params, const int* widths_host, int n_layers, int B, int nv, int C, int64_t HW, int64_t N,
+                   int K, int use_relation, int reduce, float* out, void* stream);
 
 /* ---------------- PointNet++ backwards in a fixed order (csrc/pn2_ordered.hip) ------------------------- */
 /* feature_interpolate and group_points select keys in [0, N1) through an int64 index [B,N2,K] (K = 3 for the
