@@ -100,6 +100,11 @@ _SIGNATURES = {
     "mvk_xent_workspace_floats": (C.c_int64, [_i64]),
     "mvk_xent_fwd": (C.c_int, [_vp, _i64, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "mvk_xent_bwd": (C.c_int, [_vp, _i64, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mvk_seg_workspace_floats": (C.c_int64, [_i64]),
+    "mvk_seg_loss_fwd": (C.c_int, [_vp, _i64, _i, _i64, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvk_seg_loss_fwd_f64": (C.c_int, [_vp, _i64, _i, _i64, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvk_seg_loss_bwd": (C.c_int, [_vp, _i64, _i, _i64, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvk_seg_loss_bwd_f64": (C.c_int, [_vp, _i64, _i, _i64, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvk_bn_lrelu_fwd": (C.c_int, [_vp, _vp, _i64, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _vp, _i, _vp]),
     "mvk_bn_lrelu_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]),

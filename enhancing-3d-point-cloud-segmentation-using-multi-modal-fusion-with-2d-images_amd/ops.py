@@ -2748,6 +2748,136 @@ def cross_entropy_lut(logits, labels, lut, class_weight=None):
     return _XentFn.apply(logits, labels, lut, None if class_weight is None else class_weight.contiguous())
 
 
+# --------------------------------------------------------------------------------------------
+# MVPNet baseline: segmentation loss and metrics on channel-first logits (csrc/loss.hip, seg_*)
+# --------------------------------------------------------------------------------------------
+_SEG_STATUS = {}
+
+
+def seg_label_status(device):
+    """The int32 status word (on `device`) that the segmentation loss sets to 1 when it meets a label that is neither
+    ignore_index nor a class number. One word per device, allocated on first use."""
+    device = torch.device(device)
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    if key not in _SEG_STATUS:
+        _SEG_STATUS[key] = torch.zeros((1,), device=device, dtype=torch.int32)
+    return _SEG_STATUS[key]
+
+
+def seg_check_labels(device=None):
+    """Read the status word back (this waits for the device), clear it, and raise when a seg_loss / seg_stats call since
+    the last check met a label outside [0, C) that was not ignore_index. Such a label is left out of the loss, the counts
+    and the gradient (torch's own kernel device-asserts on it); call this where a wait is affordable."""
+    status = seg_label_status(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
+    bad = int(status.item())
+    status.zero_()
+    if bad:
+        raise RuntimeError("seg_loss: a label lies outside [0, C) and is not ignore_index")
+
+
+def _seg_operands(name, logits, labels, weight):
+    """Contiguous detached operands: logits (B, C, S) float32 / float64, labels int32 / int64, weight of the logits' type."""
+    if not logits.is_floating_point() or logits.dim() < 2:
+        raise RuntimeError("%s: logits must be a floating (B, C, *) tensor" % name)
+    if labels.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError("%s: labels must be int32 or int64, got %s" % (name, labels.dtype))
+    if labels.dim() != logits.dim() - 1 or labels.shape[0] != logits.shape[0] \
+            or tuple(labels.shape[1:]) != tuple(logits.shape[2:]):
+        raise RuntimeError("%s: logits (B, C, *) and labels (B, *) expected, got %s and %s"
+                           % (name, tuple(logits.shape), tuple(labels.shape)))
+    Cc = logits.shape[1]
+    if Cc < 1 or Cc > 256:
+        raise RuntimeError("%s: 1 to 256 classes are supported, got C = %d" % (name, Cc))
+    _dev(logits, labels, weight)
+    if labels.device != logits.device:
+        raise RuntimeError("%s: labels on %s, logits on %s" % (name, labels.device, logits.device))
+    x = logits.detach()
+    if x.dtype not in (torch.float32, torch.float64):
+        x = x.float()
+    x = x.contiguous()
+    if weight is not None:
+        if weight.dim() != 1 or weight.numel() != Cc or not weight.is_floating_point():
+            raise RuntimeError("%s: weight must be a floating tensor of C = %d elements" % (name, Cc))
+        weight = weight.detach().to(x.dtype).contiguous()
+    S = 1
+    for d in x.shape[2:]:
+        S *= int(d)
+    return x, labels.detach().contiguous(), weight, int(x.shape[0]), int(Cc), S
+
+
+def _seg_int_outputs(Cc, device):
+    buf = torch.zeros((2 + Cc * Cc,), device=device, dtype=torch.int64)      # one fill for both
+    return buf[:2], buf[2:].view(Cc, Cc)
+
+
+def _seg_forward(x, labels, weight, B, Cc, S, ignore_index, with_stats, want_lse):
+    f64 = x.dtype == torch.float64
+    part = torch.empty((lib().mvk_seg_workspace_floats(B * S),), device=x.device, dtype=x.dtype)
+    out2 = torch.empty((2,), device=x.device, dtype=x.dtype)
+    lse = torch.empty((B * S,), device=x.device, dtype=x.dtype) if want_lse else None
+    counts, conf = _seg_int_outputs(Cc, x.device) if with_stats else (None, None)
+    fn = lib().mvk_seg_loss_fwd_f64 if f64 else lib().mvk_seg_loss_fwd
+    check(fn(_p(x), B, Cc, S, _p(labels), int(labels.dtype == torch.int64), int(ignore_index), _p(weight), _p(part), _p(out2),
+             _p(lse), _p(counts), _p(conf), _p(seg_label_status(x.device)), _stream()))
+    return out2, lse, counts, conf
+
+
+class _SegLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, ops_, ignore_index, with_stats):
+        x, labels, weight, B, Cc, S = ops_
+        out2, lse, counts, conf = _seg_forward(x, labels, weight, B, Cc, S, ignore_index, with_stats, True)
+        ctx.save_for_backward(x, labels, weight, out2, lse)
+        ctx.geom = (B, Cc, S, int(ignore_index), logits.dtype)
+        loss = out2[0].to(logits.dtype)
+        if not with_stats:
+            return loss
+        ctx.mark_non_differentiable(counts, conf)
+        return loss, counts, conf
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        x, labels, weight, out2, lse = ctx.saved_tensors
+        B, Cc, S, ignore_index, dtype = ctx.geom
+        g = g.to(x.dtype).contiguous()
+        d = torch.empty_like(x)                                              # every element is written
+        fn = lib().mvk_seg_loss_bwd_f64 if x.dtype == torch.float64 else lib().mvk_seg_loss_bwd
+        check(fn(_p(x), B, Cc, S, _p(labels), int(labels.dtype == torch.int64), ignore_index, _p(weight), _p(out2), _p(lse),
+                 _p(g), _p(d), _stream()))
+        return d.to(dtype), None, None, None
+
+
+def seg_loss(logits, labels, weight=None, ignore_index=-100, with_stats=True):
+    """The MVPNet baseline's segmentation loss (mvpnet/models/loss.py: F.cross_entropy(logits, labels, weight,
+    ignore_index), weighted mean over the kept points) as one autograd node over one fused launch plus the ordered finish.
+    logits (B, C, *) float32 or float64 (other floating types are converted to float32), labels (B, *) int32 / int64,
+    weight [C] or None. Returns the scalar loss, and with with_stats (loss, (counts, conf)): counts int64 [2] =
+    (kept points whose prediction equals the label, kept points), conf int64 [C, C] with rows = label and columns =
+    prediction (the first maximal class), both in HBM. A point is kept when its label is not ignore_index and lies in
+    [0, C); other labels set the status word of seg_check_labels and are left out. Nothing here reads the device back.
+    When no gradient is wanted (torch.no_grad(), or logits that do not require one) nothing is saved and no per-point
+    log-sum-exp is written."""
+    ops_ = _seg_operands("seg_loss", logits, labels, weight)
+    if torch.is_grad_enabled() and logits.requires_grad:
+        out = _SegLossFn.apply(logits, ops_, int(ignore_index), bool(with_stats))
+        return (out[0], (out[1], out[2])) if with_stats else out
+    x, labels, weight, B, Cc, S = ops_
+    out2, _, counts, conf = _seg_forward(x, labels, weight, B, Cc, S, ignore_index, with_stats, False)
+    loss = out2[0].to(logits.dtype)
+    return (loss, (counts, conf)) if with_stats else loss
+
+
+def seg_stats(logits, labels, ignore_index=-100):
+    """The metrics-only form of seg_loss: (counts int64 [2], conf int64 [C, C]) in HBM from one launch that computes the
+    predictions only (no exp, no loss). Same label rules, same status word, no device-to-host read."""
+    x, labels, _, B, Cc, S = _seg_operands("seg_stats", logits, labels, None)
+    counts, conf = _seg_int_outputs(Cc, x.device)
+    fn = lib().mvk_seg_loss_fwd_f64 if x.dtype == torch.float64 else lib().mvk_seg_loss_fwd
+    check(fn(_p(x), B, Cc, S, _p(labels), int(labels.dtype == torch.int64), int(ignore_index), None, None, None, None,
+             _p(counts), _p(conf), _p(seg_label_status(x.device)), _stream()))
+    return counts, conf
+
+
 def bias_act_nhwc(x, bias, res=None, bias2=None, relu=True, out=None):
     """act(x + bias[c] (+ res (+ bias2[c]))) on a channels-last 4-D tensor (in place unless `out`): the pointwise
     tail of a convolution of the frozen 2D encoder after its BatchNorm was folded into the weights."""

@@ -382,6 +382,35 @@ int mvk_xent_fwd(const float* logits /* [N,C] */, int64_t N, int C, const void* 
 int mvk_xent_bwd(const float* logits, int64_t N, int C, const void* labels, int labels64, const int32_t* lut, int lut_n,
                  const float* class_weight, const float* out2, const float* grad_loss, float* dlogits, void* stream);
 
+/* Segmentation loss and metrics of the MVPNet baseline (mvpnet/models/loss.py, metric.py) on channel-first logits
+ * [B, C, S] (S = the product of the trailing dimensions) and labels [B, S], 1 <= C <= 256, in one launch plus the ordered
+ * finish. A point is kept when its label differs from ignore_index and lies in [0, C); ignore_index wins when it is a
+ * class number; a label that is neither sets *status (device int32, may be NULL) to 1 and is left out like an ignored
+ * one. Over the kept points:
+ *   out2[0]  = sum w[t_i] (lse_i - x[b, t_i, s]) / sum w[t_i],  out2[1] = sum w[t_i]   (class_weight NULL: 1; 0/0 = NaN)
+ *   lse[i]   = log sum_c exp(x[b, c, s])            (one element per point, for the backward; NULL: not stored)
+ *   counts  += (#points with pred == label, #points), pred = the lowest class index among the maximal logits
+ *   conf[label * C + pred] += 1                     (int64 [C, C], rows = label)
+ * counts and conf are ACCUMULATED into (the caller zeroes them); either may be NULL. partials:
+ * mvk_seg_workspace_floats(B * S) elements of the logits' type. With partials, out2 and lse all NULL this is the
+ * metrics-only form (no exp; class_weight is not read). NaN logits are outside the contract. The loss is bit-equal from
+ * run to run (no float atomics); the counts are integer sums. */
+int64_t mvk_seg_workspace_floats(int64_t points);
+int mvk_seg_loss_fwd(const float* logits, int64_t B, int C, int64_t S, const void* labels, int labels64, int64_t ignore_index,
+                     const float* class_weight, float* partials, float* out2, float* lse, int64_t* counts, int64_t* conf,
+                     int32_t* status, void* stream);
+int mvk_seg_loss_fwd_f64(const double* logits, int64_t B, int C, int64_t S, const void* labels, int labels64,
+                         int64_t ignore_index, const double* class_weight, double* partials, double* out2, double* lse,
+                         int64_t* counts, int64_t* conf, int32_t* status, void* stream);
+/* dlogits[b, c, s] = grad_loss[0] * w[t_i] / out2[1] * (exp(x[b, c, s] - lse[i]) - [c == t_i]); 0 for every class of a
+ * point that is not kept. out2 and lse as the forward left them. */
+int mvk_seg_loss_bwd(const float* logits, int64_t B, int C, int64_t S, const void* labels, int labels64, int64_t ignore_index,
+                     const float* class_weight, const float* out2, const float* lse, const float* grad_loss, float* dlogits,
+                     void* stream);
+int mvk_seg_loss_bwd_f64(const double* logits, int64_t B, int C, int64_t S, const void* labels, int labels64,
+                         int64_t ignore_index, const double* class_weight, const double* out2, const double* lse,
+                         const double* grad_loss, double* dlogits, void* stream);
+
 /* Gradient value clipping + SGD (momentum, weight decay; torch.optim.SGD semantics, dampening 0, no Nesterov) over
  * ALL parameter tensors in one launch (utils/trainer.py:190-195: clip_grad_value_ + optimizer.step; groups with
  * their own learning rate as built at trainer.py:72-79):
