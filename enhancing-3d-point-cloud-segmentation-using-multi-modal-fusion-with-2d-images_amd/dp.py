@@ -229,7 +229,7 @@ def two_stage_backward(loss, cut_tensors, between=None, backward_scope=None, see
     detached leaves). Stage 1 = loss.backward(): gradients of the parameters above the cut and of the leaves;
     `between()` (e.g. start the all-reduce of the late bucket); stage 2 = backward of the originals with the leaves'
     gradients: the parameters below the cut. The sum of both stages is exactly what an unsevered loss.backward()
-    computes. backward_scope: context manager factory wrapped around each stage (ops.overlap_weight_grads).
+    computes. backward_scope: context manager factory wrapped around each stage (step.backward_scope).
     seed: gradient of the loss to start from (BucketedAllReduce.seed). retain_graph: see deformable_below()."""
     import contextlib
     scope = backward_scope if backward_scope is not None else contextlib.nullcontext

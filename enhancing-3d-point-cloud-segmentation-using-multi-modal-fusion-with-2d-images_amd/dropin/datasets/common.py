@@ -7,8 +7,6 @@ the stacked points stay in HBM and every level is produced by the HIP kernels (o
 subsampling level for the data-dependent point counts). NumPy inputs are accepted too (they are
 staged once) and NumPy outputs can be requested with ``as_numpy=True`` for calibration code.
 """
-import os
-
 import numpy as np
 import torch
 
@@ -131,15 +129,14 @@ def segmentation_inputs_sphere(config, stacked_points, stack_lengths, neighborho
     one cell grid.
 
     Not in the reference: ``orders`` -- per layer the level's rows sorted by the cells of its conv search's grid
-    (ops.neighbors_cell_order; None for a layer without conv blocks), the work list the KPConv gather walks
-    (MVK_GATHER_ORDER=0: no lists). The reference's flat batch list has no slot for them: each list is also
+    (ops.neighbors_cell_order; None for a layer without conv blocks), the work list the KPConv gather walks.
+    The reference's flat batch list has no slot for them: each list is also
     remembered under its points tensor (ops.remember_work_order), where the blocks find it as long as that tensor
     reaches the network as it is (device-resident batches in the process that built them).
     ``rev_neighbors`` / ``rev_pools`` -- per layer the transposed conv / pool neighbour matrix of the rigid layers
     (ops.reverse_neighbors; None elsewhere): the feature gradient of those convolutions then runs as a gather in a fixed
     summation order instead of an atomic scatter (MVK_REVERSE_DX=0: none). With ``status`` they are built at a fixed width
     and ``rev_status`` collects their overflow word (ops.check_reverse_status)."""
-    want_orders = os.environ.get("MVK_GATHER_ORDER", "1") != "0"
     grid_of = [None, None]          # supports tensor and radius of the grid the neighbour workspace holds
 
     def neighbors(qp, sp, qb, sb, radius, layer):
@@ -175,7 +172,7 @@ def segmentation_inputs_sphere(config, stacked_points, stack_lengths, neighborho
         conv_i, order = empty_idx(), None
         if e['conv_r'] is not None:
             conv_i = neighbors(pts, pts, lens, lens, e['conv_r'], layer)
-            if want_orders and pts.shape[0] > 0 and conv_i.shape[1] > 0:      # the workspace holds this search's grid
+            if pts.shape[0] > 0 and conv_i.shape[1] > 0:      # the workspace holds this search's grid
                 order = ops.neighbors_cell_order(pts.shape[0], pts.shape[0], len(lens), device=pts.device)
                 ops.remember_work_order(pts, order)      # for batch containers without an `orders` attribute
         if e['pool']:
@@ -189,12 +186,9 @@ def segmentation_inputs_sphere(config, stacked_points, stack_lengths, neighborho
             pool_p = torch.zeros((0, 3), dtype=torch.float32, device=dev)
             pool_b = np.zeros((0,), dtype=np.int32)
         # transposed relations for the gather-form feature gradient (ops.reverse_neighbors): rigid convolutions, and since
-        # round 5 the deformable ones too (searched at the wide deform radius: rows of hundreds of entries;
-        # MVK_REVERSE_DX_DEFORM=0 keeps their atomic scatter)
-        rigid = want_rev and pts.is_cuda and (not e['deform'] or ops.REVERSE_DX_DEFORM)
-
+        # round 5 the deformable ones too (searched at the wide deform radius: rows of hundreds of entries)
         def reverse(m):
-            if not rigid or m.shape[0] == 0 or m.shape[1] == 0:
+            if not (want_rev and pts.is_cuda) or m.shape[0] == 0 or m.shape[1] == 0:
                 return None
             if status is None:
                 return ops.reverse_neighbors(m, pts.shape[0])               # exact width (one read-back)

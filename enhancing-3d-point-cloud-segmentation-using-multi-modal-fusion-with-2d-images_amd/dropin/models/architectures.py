@@ -1,8 +1,6 @@
 """KPFCNN segmentation network, baseline variant (reference KPConv-PyTorch/models/architectures.py:
 p2p_fitting_regularizer :25-58, KPFCNN :189-394). Module / parameter names match the reference
 (encoder_blocks.N.*, decoder_blocks.N.*, head_mlp.*, head_softmax.*) for state-dict compatibility."""
-import os
-
 import numpy as np
 import torch
 import torch.nn as nn
@@ -15,12 +13,6 @@ except ImportError:
     from _native import ops as _ops
 
 
-_FUSED_REG = os.environ.get("MVK_FUSED_REGULARIZER", "1") == "1"   # development switch: 0 = the tensor-op form below
-_FUSED_LOSS = os.environ.get("MVK_FUSED_LOSS", "1") == "1"         # development switch: 0 = torch.nn.CrossEntropyLoss
-_FUSED_UPSAMPLE = os.environ.get("MVK_FUSED_UPSAMPLE", "1") == "1"  # development switch: 0 = closest_pool, then torch.cat
-_FUSED_UPSAMPLE_LINEAR = os.environ.get("MVK_FUSED_UPSAMPLE_LINEAR", "1") == "1"   # ... and the unary layer behind them: one backward product
-
-
 def p2p_fitting_regularizer(net):
     """Deformable-kernel regulariser (architectures.py:25-58): fitting loss = mean |min_d2| / extent^2
     (kernel point -> closest input point) and repulsive loss between the deformed kernel points of a
@@ -30,7 +22,7 @@ def p2p_fitting_regularizer(net):
     On the GPU each layer's term and both its gradients come from ONE launch (ops.deform_regularizer)."""
     total = 0
     deform = [m for m in net.modules() if isinstance(m, KPConv) and m.deformable]
-    if _FUSED_REG and deform and all(m.min_d2.is_cuda for m in deform):
+    if deform and all(m.min_d2.is_cuda for m in deform):
         # one launch per layer each way (csrc/deform.hip), all layers one autograd node accumulating into one scalar
         term = _ops.deform_regularizer_all([(m.min_d2, m.deformed_KP, m.KP_extent, net.repulse_extent,
                                              net.deform_fitting_power, _ops.row_count_for(m.min_d2.shape[0]))
@@ -153,7 +145,7 @@ class _SegmentationLossMixin:
         return lut
 
     def loss(self, outputs, labels):
-        if _FUSED_LOSS and outputs.is_cuda and outputs.dtype == torch.float32:
+        if outputs.is_cuda and outputs.dtype == torch.float32:
             # label renumbering + weighted cross entropy + mean as one autograd node (csrc/loss.hip)
             self.output_loss = _ops.cross_entropy_lut(outputs, labels, self._label_table(outputs.device, torch.int32),
                                                       self.criterion.weight)
@@ -216,11 +208,11 @@ def run_decoder(net, x, skip_x, batch):
         if block_i in net.decoder_concats and not joined:
             x = torch.cat([x, skip_x.pop()], dim=1)
         joined = False
-        if _FUSED_UPSAMPLE and isinstance(block_op, NearestUpsampleBlock) and (block_i + 1) in net.decoder_concats \
+        if isinstance(block_op, NearestUpsampleBlock) and (block_i + 1) in net.decoder_concats \
                 and x.is_cuda and block_i not in net.decoder_concats:
             inds, skip = batch.upsamples[block_op.layer_ind - 1], skip_x.pop()
             nxt = blocks[block_i + 1] if block_i + 1 < len(blocks) else None
-            if _FUSED_UPSAMPLE_LINEAR and isinstance(nxt, UnaryBlock) and torch.is_grad_enabled() and net.training:
+            if isinstance(nxt, UnaryBlock) and torch.is_grad_enabled() and net.training:
                 pending = (x, inds, skip)
                 continue
             # nearest upsampling + the concatenation that follows it (:334-335) as one launch

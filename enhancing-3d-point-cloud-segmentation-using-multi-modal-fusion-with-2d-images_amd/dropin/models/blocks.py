@@ -9,7 +9,6 @@ Same class names, constructor arguments, attribute names and state-dict keys as 
 kernel, f32 MFMA contraction, scatter backward.
 """
 import math
-import os
 
 import numpy as np
 import torch
@@ -25,29 +24,15 @@ except ImportError:  # dropin/ put on sys.path directly
     from kernels.kernel_points import load_kernels
 
 
-_FUSE_ADD = os.environ.get("MVK_FUSE_ADD", "1") == "1"      # development switches for A/B timing
-_HIP_BN = os.environ.get("MVK_HIP_BN", "1") == "1"          # training-mode BatchNorm on the masked HIP kernel (0: nn.BatchNorm1d)
-_GEMM_STATS = os.environ.get("MVK_GEMM_STATS", "1") == "1"  # BatchNorm statistics from the producing GEMM's epilogue
-_FUSE_FANOUT = os.environ.get("MVK_FUSE_FANOUT", "1") == "1"    # the two gradients of a block's input summed inside unary1's backward GEMM
-_FUSED_BIAS = os.environ.get("MVK_FUSED_BIAS", "1") == "1"      # bias + LeakyReLU of the BatchNorm-less layers in one launch
-_FUSED_OPERANDS = os.environ.get("MVK_FUSED_DEFORM_OPERANDS", "1") == "1"   # development switch: 0 = the tensor ops
-_GEMM_PAIR = os.environ.get("MVK_GEMM_PAIR", "1") == "1"        # unary1 and the shortcut layer of a block (same input) as one GEMM launch
-_BN_PAIR = os.environ.get("MVK_BN_PAIR", "1") == "1"            # a block's two independent BatchNorms (convolution, shortcut) as one launch each way
-_BN_FOLD_CONV = os.environ.get("MVK_BN_FOLD_CONV", "1") == "1"  # batch_norm_conv + LeakyReLU inside unary2's operand load (needs MVK_BN_FOLD)
-_ORDER_LOOKUP = os.environ.get("MVK_GATHER_ORDER", "1") != "0"   # gather work lists found by their points tensor (ops.work_order_for)
-
-
 def _bn_rows(x, module, use_bn=True):
     """DEVICE row count the BatchNorm after a layer will normalise over (capacity-padded level: its valid rows;
-    otherwise all rows), or None when that BatchNorm does not run on the HIP kernel."""
+    otherwise all rows), or None when that BatchNorm does not run on the HIP kernel (eval mode, CPU tensors)."""
     if not (use_bn and module.training and x.is_cuda):
         return None
     n_valid = ops.row_count_for(x.shape[0])
-    if n_valid is None and _HIP_BN:
+    if n_valid is None:
         n_valid = ops.full_count(x.shape[0], x.device)
     return n_valid
-
-_MFMA_LINEAR = os.environ.get("MVK_MFMA_LINEAR", "1") == "1"
 
 
 # ---------------------------------------------------------------- frozen inference (no reference counterpart)
@@ -194,7 +179,7 @@ class KPConv(nn.Module):
         if self.deformable:
             # offsets from an inner rigid KPConv (blocks.py:243-266)
             raw = self.offset_conv(q_pts, s_pts, neighb_inds, x, order=order, rev=rev, rev_order=rev_order)
-            if _FUSED_OPERANDS and raw.is_cuda:        # bias, scale, kernel points (and 2 sigmoid) in one launch
+            if raw.is_cuda:        # bias, scale, kernel points (and 2 sigmoid) in one launch
                 self.offset_features, offsets, self.deformed_KP, modulations = ops.deform_operands(
                     raw, self.offset_bias, self.kernel_points, self.KP_extent, self.modulated)
             else:
@@ -269,24 +254,24 @@ class BatchNormBlock(nn.Module):
         is applied here (fused into the masked kernel in capacity-padded mode). addend: the shortcut of a
         residual block, added before that activation (blocks.py:649), in the same launch when masked."""
         fz = _frozen(self)
+        act = 1.0 if slope is None else slope
         if fz is not None and x.is_cuda and x.dim() == 2:
             # frozen statistics: scale, shift, join and activation in one launch (freeze_inference)
-            return ops.affine_lrelu(x, fz[0], fz[1], 1.0 if slope is None else slope, addend)
+            return ops.affine_lrelu(x, fz[0], fz[1], act, addend)
         if self.use_bn:
             n_valid = _bn_rows(x, self)
             if n_valid is not None:
-                # capacity-padded level (hipGraph replay): statistics over the valid rows only
-                return ops.bn_lrelu(x, n_valid, self.batch_norm, 1.0 if slope is None else slope, addend)
+                # training on the GPU: the masked kernel (capacity-padded level: statistics over the valid rows only)
+                return ops.bn_lrelu(x, n_valid, self.batch_norm, act, addend)
             # [N, C] is already BatchNorm1d's (batch, channel) layout: same statistics as the
             # reference's unsqueeze/transpose round trip (blocks.py:456-460) without the copies
             x = self.batch_norm(x)
         else:
-            if addend is None and x.is_cuda and x.dim() == 2 and x.shape[1] <= 256 and _FUSED_BIAS:
-                return ops.bias_lrelu(x, self.bias, 1.0 if slope is None else slope)     # one launch each way
+            if addend is None and x.is_cuda and x.dim() == 2 and x.shape[1] <= 256:
+                return ops.bias_lrelu(x, self.bias, act)     # one launch each way
             x = x + self.bias
         if addend is not None:
-            return ops.add_lrelu(x, addend, 1.0 if slope is None else slope) if _FUSE_ADD else \
-                nn.functional.leaky_relu(x + addend, 1.0 if slope is None else slope)
+            return ops.add_lrelu(x, addend, act)
         return x if slope is None else nn.functional.leaky_relu(x, slope)
 
     def __repr__(self):
@@ -319,53 +304,51 @@ class UnaryBlock(nn.Module):
         consumers of x are then summed inside this layer's backward GEMM (ops.linear) instead of by one more launch."""
         # nn.Linear(bias=False) = x @ W^T: on the f32 MFMA GEMM (faster than the library GEMM on these
         # tall-skinny shapes, tools/gemm_bench.py); parameters stay those of self.mlp (state-dict compatible)
-        alias = x
+        slope = 1.0 if self.no_relu else 0.1
         fz, fz_bn = _frozen(self), self.batch_norm.__dict__.get('_frozen')
         if fz is not None and fz_bn is not None and join is None and x.is_cuda and x.dim() == 2:
             # frozen BatchNorm folded into the layer: W * scale in the product, shift and activation in its store
-            y = ops.linear_bias_lrelu(x, fz, fz_bn[1], 1.0 if self.no_relu else 0.1)
-            return (y, alias) if passthrough else y
-        if (_MFMA_LINEAR and _FUSED_BIAS and x.is_cuda and not self.use_bn and join is None and not passthrough
-                and x.dim() == 2 and self.out_dim <= 256):
+            y = ops.linear_bias_lrelu(x, fz, fz_bn[1], slope)
+            return (y, x) if passthrough else y
+        if x.is_cuda and not self.use_bn and join is None and not passthrough and x.dim() == 2 and self.out_dim <= 256:
             # BatchNorm-less layer: bias and activation leave with the GEMM's store (ops.linear_bias_lrelu)
-            return ops.linear_bias_lrelu(x, self.mlp.weight, self.batch_norm.bias, 1.0 if self.no_relu else 0.1)
-        if _MFMA_LINEAR and x.is_cuda:
-            nv = _bn_rows(x, self, self.use_bn) if _GEMM_STATS else None
-            bn = self.batch_norm.batch_norm if (self.use_bn and nv is not None) else None    # statistics finished by the product
-            if passthrough and _FUSE_FANOUT and x.requires_grad:
+            return ops.linear_bias_lrelu(x, self.mlp.weight, self.batch_norm.bias, slope)
+        alias = x
+        if not x.is_cuda:
+            y = self.mlp(x)
+        else:
+            nv = _bn_rows(x, self, self.use_bn)
+            bn = self.batch_norm.batch_norm if nv is not None else None     # statistics finished by the product
+            if passthrough and x.requires_grad:
                 y, alias = ops.linear(x, self.mlp.weight, stats_n_valid=nv, passthrough=True, bn=bn)
             else:
                 y = ops.linear(x, self.mlp.weight, stats_n_valid=nv, bn=bn)
-        else:
-            y = self.mlp(x)
-        if join is not None:
-            out = self.batch_norm(y, join[1], addend=join[0])
-        else:
-            out = self.batch_norm(y, None if self.no_relu else 0.1)
+        out = self._finish(y, join)
         return (out, alias) if passthrough else out
+
+    def _finish(self, y, join):
+        """BatchNorm (or bias) and activation of the product y; join = (shortcut, slope) as in forward."""
+        if join is not None:
+            return self.batch_norm(y, join[1], addend=join[0])
+        return self.batch_norm(y, None if self.no_relu else 0.1)
 
     def forward_upsampled(self, x, inds, skip):
         """forward(cat([closest_pool(x, inds), skip], 1)): the decoder's upsampling + concatenation + this layer
         (architectures.py:334-337) with the backward of all three as one product (ops.upsample_cat_linear)."""
-        nv = _bn_rows(skip, self, self.use_bn) if _GEMM_STATS else None
+        nv = _bn_rows(skip, self, self.use_bn)
         y = ops.upsample_cat_linear(x, inds, skip, self.mlp.weight, stats_n_valid=nv,
-                                    bn=self.batch_norm.batch_norm if (self.use_bn and nv is not None) else None)
-        return self.batch_norm(y, None if self.no_relu else 0.1)
+                                    bn=self.batch_norm.batch_norm if nv is not None else None)
+        return self._finish(y, None)
 
     def forward_normalised(self, x_raw, n_valid, bn_in, slope_in, join=None):
         """forward(bn_lrelu(x_raw, n_valid, bn_in, slope_in), join=join) with the apply pass of bn_in folded into this
         layer's product (ops.bn_lrelu_linear), or None when x_raw does not carry finished statistics."""
-        if not (_MFMA_LINEAR and self.use_bn and x_raw.is_cuda):
+        if not (self.use_bn and x_raw.is_cuda):
             return None
-        nv = _bn_rows(x_raw, self, True) if _GEMM_STATS else None
+        nv = _bn_rows(x_raw, self, True)
         res = ops.bn_lrelu_linear(x_raw, n_valid, bn_in, slope_in, self.mlp.weight, stats_n_valid=nv,
                                   bn_out=self.batch_norm.batch_norm if nv is not None else None)
-        if res is None:
-            return None
-        y = res[0]
-        if join is not None:
-            return self.batch_norm(y, join[1], addend=join[0])
-        return self.batch_norm(y, None if self.no_relu else 0.1)
+        return None if res is None else self._finish(res[0], join)
 
     def __repr__(self):
         return 'UnaryBlock(in_feat: {:d}, out_feat: {:d}, BN: {:s}, ReLU: {:s})'.format(
@@ -386,7 +369,7 @@ def _work_order(block_name, layer_ind, batch):
     orders = getattr(batch, 'orders', None)
     if orders:
         return orders[l] if l < len(orders) else None
-    return ops.work_order_for(batch.points[l]) if _ORDER_LOOKUP else None
+    return ops.work_order_for(batch.points[l])
 
 
 def _reverse_list(block_name, layer_ind, batch):
@@ -401,12 +384,11 @@ def _reverse_list(block_name, layer_ind, batch):
         # batch containers without these attributes (the reference's flat input_list): the list registered under the
         # neighbour matrix itself when the pyramid was built in this process (ops.remember_reverse), like the work lists
         inds = (batch.pools if strided else batch.neighbors)[layer_ind]
-        rev = ops.reverse_for(inds) if (_ORDER_LOOKUP and ops.REVERSE_DX and torch.is_tensor(inds)) else None
+        rev = ops.reverse_for(inds) if (ops.REVERSE_DX and torch.is_tensor(inds)) else None
         if rev is None:
             return None, None
     orders = getattr(batch, 'orders', None)
-    order = orders[layer_ind] if orders and layer_ind < len(orders) else \
-        (ops.work_order_for(batch.points[layer_ind]) if _ORDER_LOOKUP else None)
+    order = orders[layer_ind] if orders and layer_ind < len(orders) else ops.work_order_for(batch.points[layer_ind])
     return rev, order
 
 
@@ -430,12 +412,12 @@ class SimpleBlock(nn.Module):
 
     def forward(self, x, batch):
         q_pts, s_pts, inds = _conv_inputs(self.block_name, self.layer_ind, batch)
-        nv = _bn_rows(q_pts, self, self.use_bn) if _GEMM_STATS else None
+        nv = _bn_rows(q_pts, self, self.use_bn)
         rev, rev_order = _reverse_list(self.block_name, self.layer_ind, batch) if x.requires_grad else (None, None)
         return self.batch_norm(self.KPConv(q_pts, s_pts, inds, x, stats_n_valid=nv,
                                            order=_work_order(self.block_name, self.layer_ind, batch), rev=rev,
                                            rev_order=rev_order,
-                                           bn=self.batch_norm.batch_norm if (self.use_bn and nv is not None) else None), 0.1)
+                                           bn=self.batch_norm.batch_norm if nv is not None else None), 0.1)
 
 
 class ResnetBottleneckBlock(nn.Module):
@@ -467,61 +449,52 @@ class ResnetBottleneckBlock(nn.Module):
 
     def forward(self, features, batch):
         q_pts, s_pts, inds = _conv_inputs(self.block_name, self.layer_ind, batch)
-        us, ys = self.unary_shortcut, None
-        if (_GEMM_PAIR and _MFMA_LINEAR and features.is_cuda and 'strided' not in self.block_name
-                and isinstance(self.unary1, UnaryBlock) and isinstance(us, UnaryBlock)):
-            # unary1 and the shortcut layer read the same rows: their two products as one launch (ops.linear_pair)
-            nv_in = _bn_rows(features, self, self.use_bn) if _GEMM_STATS else None
+        strided = 'strided' in self.block_name
+        us, bn_conv = self.unary_shortcut, self.batch_norm_conv.batch_norm if self.use_bn else None
+        # unary1 -- with the shortcut layer's product `ys` in the same launch when both read the same rows (ops.linear_pair)
+        pair = None
+        if features.is_cuda and not strided and isinstance(self.unary1, UnaryBlock) and isinstance(us, UnaryBlock):
+            nv_in = _bn_rows(features, self, self.use_bn)
             pair = ops.linear_pair(features, self.unary1.mlp.weight, us.mlp.weight, nv_in,
-                                   bn0=self.unary1.batch_norm.batch_norm if (self.use_bn and nv_in is not None) else None,
-                                   bn1=us.batch_norm.batch_norm if (self.use_bn and nv_in is not None) else None)
-            if pair is not None:
-                ys = pair[1]
-                x = self.unary1.batch_norm(pair[0], 0.1)
-        if ys is None:
-            if isinstance(self.unary1, UnaryBlock):
-                x, features = self.unary1(features, passthrough=True)  # `features` from here on: the shortcut's input
-            else:
-                x = self.unary1(features)
-        nv = _bn_rows(q_pts, self, self.use_bn) if _GEMM_STATS else None
+                                   bn0=self.unary1.batch_norm.batch_norm if nv_in is not None else None,
+                                   bn1=us.batch_norm.batch_norm if nv_in is not None else None)
+        ys = None
+        if pair is not None:
+            x, ys = self.unary1.batch_norm(pair[0], 0.1), pair[1]
+        elif isinstance(self.unary1, UnaryBlock):
+            x, features = self.unary1(features, passthrough=True)   # `features` from here on: the shortcut's input
+        else:
+            x = self.unary1(features)
+        # convolution; nv: the rows its BatchNorm runs over on the HIP kernel, None in eval mode and on the CPU
+        nv = _bn_rows(q_pts, self, self.use_bn)
         rev, rev_order = _reverse_list(self.block_name, self.layer_ind, batch)
         conv = self.KPConv(q_pts, s_pts, inds, x, stats_n_valid=nv, order=_work_order(self.block_name, self.layer_ind, batch),
-                           rev=rev, rev_order=rev_order,
-                           bn=self.batch_norm_conv.batch_norm if (self.use_bn and nv is not None) else None)
+                           rev=rev, rev_order=rev_order, bn=bn_conv if nv is not None else None)
+        # shortcut pooling
         self.skip_alias = None
-        if 'strided' in self.block_name and _FUSE_FANOUT and features.is_cuda:
+        if strided and features.is_cuda:
             # the block's input is also the decoder's skip tensor (architectures.py:328-329): the alias handed out here
             # lets the pooling's backward accumulate onto the decoder's gradient (run_encoder_decoder picks it up)
             shortcut, self.skip_alias = ops.max_pool(features, inds, passthrough=True)
         else:
-            shortcut = max_pool(features, inds) if 'strided' in self.block_name else features
-        n_valid = _bn_rows(conv, self, self.use_bn) if (_BN_PAIR and _HIP_BN and _MFMA_LINEAR) else None
-        if _BN_FOLD_CONV and _FUSE_ADD and n_valid is not None and ops.bn_finished(conv):
-            # the convolution's statistics were finished by its contraction: its BatchNorm + LeakyReLU ride in unary2's
-            # operand load (ops.bn_lrelu_linear) -- no normalising launch for the convolution at all
-            if isinstance(us, UnaryBlock):
-                sc = us(shortcut) if ys is None else us.batch_norm(ys, None)
-            else:
-                sc = shortcut
-            out = self.unary2.forward_normalised(conv, n_valid, self.batch_norm_conv.batch_norm, 0.1, join=(sc, 0.1))
-            if out is not None:
-                return out
-            shortcut = sc
-            x = self.batch_norm_conv(conv, 0.1)
-            return self.unary2(x, join=(shortcut, 0.1))
-        if n_valid is not None and isinstance(us, UnaryBlock) and us.use_bn:
+            shortcut = max_pool(features, inds) if strided else features
+        if ops.bn_finished(conv):
+            # the convolution's statistics were finished by its contraction (ops.BN_FOLD): its BatchNorm + LeakyReLU ride
+            # in unary2's operand load (ops.bn_lrelu_linear) -- no normalising launch for the convolution at all
+            shortcut = us(shortcut) if ys is None else us.batch_norm(ys, None)
+            out = self.unary2.forward_normalised(conv, nv, bn_conv, 0.1, join=(shortcut, 0.1))
+            return out if out is not None else self.unary2(self.batch_norm_conv(conv, 0.1), join=(shortcut, 0.1))
+        if nv is not None and isinstance(us, UnaryBlock) and us.use_bn:
             # the BatchNorm of the convolution and the one of the shortcut are independent problems over the same rows:
             # one launch each way for the pair (ops.bn_lrelu_pair)
             if ys is None:
-                ys = ops.linear(shortcut, us.mlp.weight, stats_n_valid=n_valid if _GEMM_STATS else None)
-            x, shortcut = ops.bn_lrelu_pair(conv, self.batch_norm_conv.batch_norm, 0.1, ys, us.batch_norm.batch_norm, 1.0,
-                                            n_valid)
+                ys = ops.linear(shortcut, us.mlp.weight, stats_n_valid=nv)
+            x, shortcut = ops.bn_lrelu_pair(conv, bn_conv, 0.1, ys, us.batch_norm.batch_norm, 1.0, nv)
         else:
             x = self.batch_norm_conv(conv, 0.1)
             shortcut = us(shortcut) if ys is None else us.batch_norm(ys, None)
-        if _FUSE_ADD:       # x = unary2(x); return leaky_relu(x + shortcut)  (blocks.py:644-649), join fused
-            return self.unary2(x, join=(shortcut, 0.1))
-        return self.leaky_relu(self.unary2(x) + shortcut)
+        # x = unary2(x); return leaky_relu(x + shortcut)  (blocks.py:644-649), the join inside unary2's BatchNorm launch
+        return self.unary2(x, join=(shortcut, 0.1))
 
 
 class GlobalAverageBlock(nn.Module):

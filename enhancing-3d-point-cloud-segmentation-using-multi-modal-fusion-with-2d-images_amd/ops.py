@@ -107,7 +107,7 @@ def _zeros(shape, device, dtype=torch.float32):
 # the BatchNorm-less layers is summed in workgroup order, outputs need no zero fill and split plans keep their
 # BatchNorm-statistics epilogue. The price is three memory-side round trips at the tail of every split launch (~4 us
 # each, +0.2 ms on the 4.1 ms early-fusion step): opt-in, like torch.use_deterministic_algorithms.
-_DET = {"on": os.environ.get("MVK_DETERMINISTIC", os.environ.get("MVK_GEMM_ORDERED", "0")) == "1"}
+_DET = {"on": os.environ.get("MVK_DETERMINISTIC", "0") == "1"}
 _SPLIT_ARENA = {}
 _SPLIT_ARENA_BYTES = int(os.environ.get("MVK_GEMM_ARENA_MB", "1024")) << 20
 _SPLIT_COUNTERS = 1 << 20
@@ -543,54 +543,11 @@ def kpconv_gather_rev_deform(s, q, rev, g, kp, extent, offsets, modulations=None
 # --------------------------------------------------------------------------------------------
 # The backward of a layer launches two independent products, dW = A^T g and dA = g W^T; only dA feeds the rest
 # of the backward chain, dW is not read before the optimiser. Every product here is a small, latency-bound
-# launch (~10 us whatever its size), so inside `with overlap_weight_grads():` the dW products are enqueued on a
-# side stream forked from the current one (a parallel branch of the captured hipGraph) and joined when the scope
-# ends -- about a hundred launches leave the serial chain of a step. Opt-in: gradients must not be read (or
-# accumulated into an existing .grad) before the scope has been left.
-_OVERLAP = {"on": False, "streams": None, "i": 0, "used": []}
-
-
-class overlap_weight_grads:
-    def __init__(self, n_streams=2):
-        self.n = int(n_streams)
-
-    def __enter__(self):
-        if _OVERLAP["streams"] is None or len(_OVERLAP["streams"]) != self.n:
-            _OVERLAP["streams"] = [torch.cuda.Stream() for _ in range(self.n)]
-        _OVERLAP.update(on=True, i=0, used=[])
-        return self
-
-    def __exit__(self, *exc):
-        cur = torch.cuda.current_stream()
-        for st in _OVERLAP["used"]:
-            cur.wait_stream(st)
-        _OVERLAP.update(on=False, used=[])
-        return False
-
-
-def _gemm_off_chain(A, B, **kw):
-    """gemm() whose result nothing on the current stream reads before the overlap scope is left (a weight gradient)."""
-    if not _OVERLAP["on"]:
-        return gemm(A, B, **kw)
-    cur = torch.cuda.current_stream()
-    side = _OVERLAP["streams"][_OVERLAP["i"] % len(_OVERLAP["streams"])]
-    _OVERLAP["i"] += 1
-    side.wait_stream(cur)
-    with torch.cuda.stream(side):
-        out = gemm(A, B, **kw)
-    for t in (A, B):
-        t.record_stream(side)          # their memory must not be recycled by the current stream while the side product runs
-    out.record_stream(cur)
-    if side not in _OVERLAP["used"]:
-        _OVERLAP["used"].append(side)
-    return out
-
-
-# ---- all weight gradients of a backward pass in (at most) two launches ------------------------------------
+# launch (~10 us whatever its size), so all weight gradients of a backward pass run as (at most) two launches:
 # `with defer_weight_grads(): loss.backward()`: every dW product of the pass is only RECORDED (its zero-initialised
 # result tensor is handed to autograd at once) and the whole list runs as one grouped launch per tile shape when the
-# scope ends (mvk_gemm_f32_tn_grouped): ~100 latency-bound ~10 us launches leave the serial chain of a step. Same
-# contract as overlap_weight_grads: nothing may read a weight gradient before the scope has been left.
+# scope ends (mvk_gemm_f32_tn_grouped): ~100 latency-bound ~10 us launches leave the serial chain of a step. Opt-in:
+# nothing may read a weight gradient (or accumulate into an existing .grad) before the scope has been left.
 _DEFER = {"on": False, "items": [], "leaves": set(), "slots": None, "eager": 0}
 _DW_MAX = 512
 
@@ -716,10 +673,8 @@ def _accumulate_in_place_ok(t):
     """Whether a backward node may ADD onto its incoming gradient `t` in place (the fan-out sums of _LinearFn /
     _MaxPoolFn). Autograd hands the SAME tensor to every consumer of an addition's gradient (AddBackward, and
     _AddLReLUFn before it returned copies), so `t` may also be an operand of a weight-gradient product that has only
-    been RECORDED (defer_weight_grads) or enqueued on a side stream (overlap_weight_grads): mutating it first would
-    corrupt that product silently. Not provably exclusive -> the caller computes `product + t` instead."""
-    if _OVERLAP["on"]:
-        return False
+    been RECORDED (defer_weight_grads): mutating it first would corrupt that product silently. Not provably
+    exclusive -> the caller computes `product + t` instead."""
     if _DEFER["on"] and _DEFER["items"]:
         st = t.untyped_storage().data_ptr()
         for it in _DEFER["items"]:
@@ -729,9 +684,8 @@ def _accumulate_in_place_ok(t):
 
 
 def _dw_gemm(A, B, transB=False, target=None):
-    """A^T @ B for a weight gradient: deferred into the grouped launch inside defer_weight_grads(), on a side stream
-    inside overlap_weight_grads(), a plain product otherwise. `target`: the tensor the gradient is FOR (the Function's
-    weight input). A deferred product hands autograd a result that is only computed when the scope ends, which is
+    """A^T @ B for a weight gradient: deferred into the grouped launch inside defer_weight_grads(), a plain product
+    otherwise. `target`: the tensor the gradient is FOR (the Function's weight input). A deferred product hands autograd a result that is only computed when the scope ends, which is
     sound only if AccumulateGrad ADOPTS that tensor as the parameter's .grad: a parameter that already holds a gradient
     (zero_grad(set_to_none=False), micro-batch accumulation, a second backward stage through the same weight) would
     get `grad += <not yet computed>` and the result tensor would be freed before the grouped launch writes it -- such
@@ -742,7 +696,7 @@ def _dw_gemm(A, B, transB=False, target=None):
             raise RuntimeError("defer_weight_grads: the same parameter receives two weight gradients inside one scope "
                                "(shared weights): run this backward without the scope (MVK_DEFER_DW=0)")
         if leaf.grad is not None:
-            return _gemm_off_chain(A, B, transA=True, transB=transB)
+            return gemm(A, B, transA=True, transB=transB)
     if _DEFER["on"] and _HAS_USE_COUNT and not transB and A.is_cuda and B.shape[1] > 16 and len(_DEFER["items"]) < _DW_MAX \
             and A.shape[0] > 0 and A.shape[1] > 0:
         A, B = _f32c(A), _f32c(B)
@@ -762,7 +716,7 @@ def _dw_gemm(A, B, transB=False, target=None):
         if leaf is not None:
             _DEFER["leaves"].add(id(leaf))
         return out
-    return _gemm_off_chain(A, B, transA=True, transB=transB)
+    return gemm(A, B, transA=True, transB=transB)
 
 
 # --------------------------------------------------------------------------------------------
@@ -820,30 +774,14 @@ class _KPConvFn(torch.autograd.Function):
         rev, rev_order = ctx.rev
         gather_form = (need_dA and rev is not None and REVERSE_DX and rev.shape[0] >= s.shape[0] and Cout >= 5
                        and influence == "linear" and aggregation == "sum")
-        if gather_form and offsets is None and modulations is None and (Cout >= 32 or REVERSE_DX_ANY_COUT):
+        if gather_form and rev.shape[0] != s.shape[0]:
+            rev = rev[:s.shape[0]]
+        if gather_form and offsets is None and modulations is None:
             # gather form (csrc/revlist.hip): the forward kernel over the transposed neighbourhood relation with the
             # kernel points negated, then the per-kernel-point transposed contraction -- no atomics, fixed summation order
-            if rev.shape[0] != s.shape[0]:
-                rev = rev[:s.shape[0]]
             A2, _ = kpconv_gather(s, q, rev, gy, _neg_kernel_points(kp), extent, influence, aggregation, order=rev_order,
                                   tag="[dx]")
             dx = kp_transposed_contraction(A2, W)
-        elif gather_form and offsets is not None and REVERSE_DX_DEFORM:
-            # deformable layer (round 5): the same gather with the kernel points -- and modulations -- of the NEIGHBOUR rows
-            # (mvk_kpconv_gather_rev_deform); dA is still needed, by the offset gradient and the modulation gradient
-            if rev.shape[0] != s.shape[0]:
-                rev = rev[:s.shape[0]]
-            dAm = gemm(gy, W.reshape(K * Cin, Cout), transB=True).view(Nq, K, Cin)
-            if modulations is not None:
-                if ctx.needs_input_grad[7]:
-                    d_mod = (dAm * A).sum(dim=2)
-                dA = dAm * modulations.unsqueeze(2)
-            else:
-                dA = dAm
-            d_off = kpconv_deform_doff(q, s, idx, x, kp, extent, offsets, dA, g_min_d2, ctx.min_arg)
-            if ctx.needs_input_grad[3]:
-                A2 = kpconv_gather_rev_deform(s, q, rev, gy, kp, extent, offsets, modulations, order=rev_order)
-                dx = kp_transposed_contraction(A2, W)
         elif need_dA:
             dAm = gemm(gy, W.reshape(K * Cin, Cout), transB=True).view(Nq, K, Cin)
             if modulations is not None:
@@ -852,9 +790,17 @@ class _KPConvFn(torch.autograd.Function):
                 dA = dAm * modulations.unsqueeze(2)
             else:
                 dA = dAm
-            dx, d_off = kpconv_scatter(q, s, idx, dA, kp, extent, influence, aggregation, x=x,
-                                       offsets=offsets,
-                                       g_min_d2=g_min_d2 if offsets is not None else None, min_arg=ctx.min_arg)
+            if gather_form and offsets is not None:
+                # deformable layer (round 5): the same gather with the kernel points -- and modulations -- of the NEIGHBOUR
+                # rows (mvk_kpconv_gather_rev_deform); dA is still needed, by the offset gradient and the modulation gradient
+                d_off = kpconv_deform_doff(q, s, idx, x, kp, extent, offsets, dA, g_min_d2, ctx.min_arg)
+                if ctx.needs_input_grad[3]:
+                    A2 = kpconv_gather_rev_deform(s, q, rev, gy, kp, extent, offsets, modulations, order=rev_order)
+                    dx = kp_transposed_contraction(A2, W)
+            else:
+                dx, d_off = kpconv_scatter(q, s, idx, dA, kp, extent, influence, aggregation, x=x,
+                                           offsets=offsets,
+                                           g_min_d2=g_min_d2 if offsets is not None else None, min_arg=ctx.min_arg)
         return None, None, None, dx, None, dW, d_off, d_mod, None, None, None, None, None, None, None, None
 
 
@@ -873,9 +819,9 @@ def kpconv(q, s, idx, x, kp, W, extent, influence="linear", aggregation="sum", o
     of y over its first n_valid rows for the BatchNorm that follows (picked up by bn_lrelu via bn_stats_of).
     order (int32 [Nq], a permutation, e.g. neighbors_cell_order of the query level): the order the f32 gather works
     through the query points in (kpconv_gather); the layer's result does not depend on it.
-    rev (int32 [Ns, Hr], reverse_neighbors(idx, Ns)) and rev_order (a work list of the SUPPORT level): rigid f32 layers
-    with a power-of-two Cout >= 32 then compute the feature gradient as a gather over the transposed relation (fixed
-    summation order, no atomics) instead of the atomic scatter.
+    rev (int32 [Ns, Hr], reverse_neighbors(idx, Ns)) and rev_order (a work list of the SUPPORT level): f32 layers with
+    linear influence, sum aggregation and Cout >= 5 then compute the feature gradient as a gather over the transposed
+    relation (fixed summation order, no atomics) instead of the atomic scatter.
     bn: the nn.BatchNorm1d that normalises y; its statistics are then FINISHED by the contraction (when _finishable)."""
     if rev is not None and (rev.dtype != torch.int32 or rev.dim() != 2 or not rev.is_contiguous()):
         raise RuntimeError("kpconv: rev must be a contiguous int32 [Ns, Hr] matrix (ops.reverse_neighbors)")
@@ -1817,8 +1763,6 @@ def neighbors_cell_order(Nq, Ns, B, out=None, s_lens_dev=None, device=None):
 _REV_COUNTS = {}      # device index -> persistent zero int32 buffer of mvk_reverse_neighbors (self-cleaning)
 _REV_COUNTS_RETIRED = []      # outgrown buffers: a graph captured earlier still adds into and zeroes its old address
 REVERSE_DX = os.environ.get("MVK_REVERSE_DX", "1") == "1"      # development switch: 0 = the scatter backward everywhere
-REVERSE_DX_DEFORM = os.environ.get("MVK_REVERSE_DX_DEFORM", "1") == "1"     # 0: deformable layers keep the atomic scatter
-REVERSE_DX_ANY_COUT = os.environ.get("MVK_REVERSE_DX_ANY_COUT", "1") == "1"  # 0: gather form only for Cout a power of two >= 32
 
 
 def _rev_counts(n, device):
@@ -2591,9 +2535,6 @@ class _LinearFn(torch.autograd.Function):
         return dx, dW, None, None, None, None, None
 
 
-_GEMM_DUAL = os.environ.get("MVK_GEMM_DUAL", "1") == "1"
-
-
 def gemm_dual(A, B, A2, B2):
     """A @ B + A2 @ B2 (all row-major, same output shape) in one launch with the two reductions laid end to end
     (mvk_gemm_f32_dual), or None when the shape is not supported (the caller runs two products)."""
@@ -2655,7 +2596,7 @@ class _LinearPairFn(torch.autograd.Function):
         g0 = _f32c(g0) if g0 is not None else None
         g1 = _f32c(g1) if g1 is not None else None
         if ctx.needs_input_grad[0]:
-            if g0 is not None and g1 is not None and _GEMM_DUAL:
+            if g0 is not None and g1 is not None:
                 dx = gemm_dual(g0, W0, g1, W1)          # g0 W0 + g1 W1 as one launch, or None
             if dx is None:
                 if g0 is not None:

@@ -692,7 +692,7 @@ def split_tail_plan(net, cfg, opt):
     the backward of levels 0-1. MVK_SPLIT_TAIL=0: everything at the end, on the chain."""
     if os.environ.get("MVK_SPLIT_TAIL", "0") != "1" or not hasattr(net, "encoder_blocks") or not hasattr(opt, "clip"):
         return None
-    if os.environ.get("MVK_DEFER_DW", "1") != "1" or os.environ.get("MVK_OVERLAP_DW", "0") == "1":
+    if os.environ.get("MVK_DEFER_DW", "1") != "1":
         return None
     key = id(net)
     if key not in _TAIL:
@@ -730,10 +730,8 @@ def split_tail_backward(ops, net, loss, opt, tail):
 
 def backward_scope(ops):
     """Context manager factory for a backward pass: all weight-gradient products of the pass as one grouped launch at
-    its end (ops.defer_weight_grads, default), on a side branch (MVK_OVERLAP_DW=1), or in line (MVK_DEFER_DW=0)."""
+    its end (ops.defer_weight_grads, default), or in line (MVK_DEFER_DW=0)."""
     import contextlib
-    if os.environ.get("MVK_OVERLAP_DW", "0") == "1":
-        return ops.overlap_weight_grads
     return ops.defer_weight_grads if os.environ.get("MVK_DEFER_DW", "1") == "1" else contextlib.nullcontext
 
 
@@ -742,8 +740,8 @@ _DUMMY = {}
 
 
 def backward(ops, loss):
-    """loss.backward() with the weight-gradient products on a side branch (ops.overlap_weight_grads): nothing reads
-    a gradient before the optimiser (or the all-reduce), which run after the scope has joined."""
+    """loss.backward() inside backward_scope (the weight-gradient products as one grouped launch at its end): nothing
+    reads a gradient before the optimiser (or the all-reduce), which run after the scope has been left."""
     seed = _SEED.get(loss.device)
     if seed is None:        # the seed of loss.backward() -- a tensor of ones, one fill launch per call -- made once
         seed = _SEED[loss.device] = torch.ones((), device=loss.device, dtype=loss.dtype)

@@ -756,3 +756,19 @@ def test_two_stage_backward_with_bucketed_allreduce_two_gloo_ranks():
     for p in procs:
         p.join(60)
     assert all(ok for _, ok, _ in res) and res[0][2] == 5
+
+
+def test_design_switch_table_lists_exactly_the_variables_the_code_reads():
+    """DESIGN.md section 9 names every MVK_* environment variable the code reads, and nothing else. "Reads": the literal
+    passed to getenv, to os.environ[...] / os.environ.get, or to step._knob -- in the package (.py, .hip, .h, .cpp),
+    bench.py, __graft_entry__.py and tests/util.py."""
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = design[design.index("\n## 9. "):]
+    listed = set(re.findall(r"\bMVK_[A-Z0-9_]*[A-Z0-9]\b", section.split("\n## ", 2)[1]))
+    files = [os.path.join(ROOT, f) for f in ("bench.py", "__graft_entry__.py", os.path.join("tests", "util.py"))]
+    for dp, _, names in os.walk(os.path.join(ROOT, PKG)):
+        files += [os.path.join(dp, f) for f in names if f.endswith((".py", ".hip", ".h", ".cpp"))]
+    reads = re.compile(r"""(?:getenv\(|environ\.get\(|environ\[|_knob\()\s*["'](MVK_[A-Z0-9_]+)["']\s*(\]\s*=(?!=))?""")
+    read = {m.group(1) for f in files for m in reads.finditer(open(f).read()) if not m.group(2)}     # group 2: an assignment
+    assert len(read) > 50
+    assert read == listed, "read but not listed: %s; listed but not read: %s" % (sorted(read - listed), sorted(listed - read))
