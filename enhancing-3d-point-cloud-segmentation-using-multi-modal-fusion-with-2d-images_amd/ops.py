@@ -282,7 +282,9 @@ def gemm(A, B, transA=False, transB=False, out=None, accumulate=False, split_k=N
     """C = op(A) @ op(B) on v_mfma_f32_16x16x4_f32 (mvk_gemm_f32_ex). split_k=None lets the library pick the
     row tile and the split of the reduction so that small-M / deep-K products (the coarse KPConv layers:
     85 x 7680 x 512) still fill the 256 CUs. keep=True: the result outlives the step (a weight gradient that
-    becomes .grad), so it must not be a slice of the per-step zero arena.
+    becomes .grad), so it must not be a slice of the per-step zero arena. out: the caller's [M,N] buffer; without
+    `accumulate` it ends up holding the product alone whatever it held before (a split reduction that adds with atomics
+    gets it zero-filled first).
     stats_n_valid (DEVICE int32 [1]): also produce the column statistics of C over its first n_valid rows for
     the BatchNorm that follows; returns (C, (partials, rows per block)) -- or (C, None) when the chosen plan
     splits the reduction."""
@@ -320,7 +322,9 @@ def _product(A, B, *, transA=False, transB=False, out=None, accumulate=False, sp
     split, rows = gemm_plan(M, N, Kd, split_k, stats_ok)
     if out is None:
         out = _split_out((M, N), A.device, split, keep)
-    part = torch.empty(((M + rows - 1) // rows, 2, N), device=A.device, dtype=torch.float32) if rows > 0 else None
+    elif split > 1 and not accumulate and A.device.index not in _SPLIT_ARENA:
+        out.zero_()          # the atomic split adds onto the output: a caller's buffer starts from zero like our own
+    part =torch.empty(((M + rows - 1) // rows, 2, N), device=A.device, dtype=torch.float32) if rows > 0 else None
     fin = done = None
     if finish is not None and part is not None and not transA and split_k is None:
         fin, done = _fin_struct(finish, N, A.device)
