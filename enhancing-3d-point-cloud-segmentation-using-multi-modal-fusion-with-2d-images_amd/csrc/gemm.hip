@@ -1016,7 +1016,7 @@ struct GemmOpts {
   float act_slope = 1.f;
   const ScatterOut* scatter = nullptr;
   int seg_shift = -1;
-  int64_t seg_extra = 0, ldb = 0;
+  int64_t seg_extra = 0, ldb = 0, lda = 0;     // lda: A = a row (column, when transposed) block of a taller matrix
   const mvk_bn_finish* fin = nullptr;
   const mvk_a_transform* ax = nullptr;
 };
@@ -1035,8 +1035,25 @@ int gemm_run(const float* A, const float* B, float* C, int64_t M, int64_t N, int
   MVK_REQUIRE(!(o.bn_part && o.split_k > 1 && !ordered_splits()), "gemm: BatchNorm statistics need an unsplit (or ordered) reduction");
   const Plan p = plan_gemm(M, N, Kd, (o.bn_part && !ordered_splits()) ? 1 : (o.split_k > 0 ? o.split_k : 0), o.bn_part != nullptr);
   const KSplit ks = clamp_split(Kd, p.split);
+  const int64_t lda = o.lda > 0 ? o.lda : (transA ? M : Kd);
+  // More row tiles than grid.y takes (2^16 - 1; the rows of a PointNet++ level at 32 chunks): the product as row chunks,
+  // each a launch of its own with THIS plan's split (what the caller zero-filled C for). Plain products only: the
+  // statistics epilogue and its consumers stop far below such row counts. A chunk is a whole number of every row tile
+  // (16 .. 256 rows) and stays below 2^16 tiles of the smallest.
+  if (cdiv64(M, p.tm()) >= 65536) {
+    MVK_REQUIRE(!o.bn_part && !o.fin && !o.ax && !o.scatter && o.seg_shift < 0 && ks.n < 65536, "gemm: grid too large");
+    constexpr int64_t CHUNK = 15 * 65536;
+    GemmOpts oc = o;
+    oc.split_k = ks.n;
+    oc.lda = lda;
+    for (int64_t m0 = 0; m0 < M; m0 += CHUNK) {
+      const int64_t mc = M - m0 < CHUNK ? M - m0 : CHUNK;
+      if (int e = gemm_run(A + (transA ? m0 : m0 * lda), B, C + m0 * N, mc, N, Kd, transA, transB, oc, stream)) return e;
+    }
+    return 0;
+  }
   // o.ldb: B = a column block of a wider matrix
-  GemmArgs a = make_args(A, B, C, M, N, Kd, transA ? M : Kd, o.ldb > 0 ? o.ldb : (transB ? Kd : N), ks);
+  GemmArgs a = make_args(A, B, C, M, N, Kd, lda, o.ldb > 0 ? o.ldb : (transB ? Kd : N), ks);
   if (o.seg_shift >= 0) {
     a.ldb = (int64_t)1 << o.seg_shift;        // rows of W[k]: Cout floats
     a.vecB = ((uintptr_t)B % 16 == 0 && o.seg_extra % 4 == 0) ? 4 : 1;

@@ -1,10 +1,13 @@
 """PointNet++ building blocks of the MVPNet baseline (reference mvpnet/models/pn2/modules.py) on the HIP point ops:
 farthest point sampling, ball query, grouping, 3-NN and interpolation are kernels of csrc/pn2.hip / fusion.hip; the
-shared 1x1 convolutions, BatchNorm and the max over neighbours stay PyTorch ops, except after freeze_inference, when a
-SetAbstraction or FeaturePropagation in eval mode under torch.no_grad() is its point search plus ONE fused launch
-(csrc/pn2_mlp.hip). Sub-module names match the reference so its checkpoints load."""
+shared 1x1 convolutions, BatchNorm and the max over neighbours stay PyTorch ops, except (a) after freeze_inference, when
+a SetAbstraction or FeaturePropagation in eval mode under torch.no_grad() is its point search plus ONE fused launch
+(csrc/pn2_mlp.hip), and (b) after fuse_training, when their training-mode shared MLPs run on the library's GEMM and
+BatchNorm between the row builder and the max of csrc/pn2_train.hip. Sub-module names match the reference so its
+checkpoints load."""
 import torch
 from torch import nn
+import torch.nn.functional as F
 
 try:
     from ....common.nn import SharedMLP, batch_index_select
@@ -124,6 +127,96 @@ def unfreeze_inference(net):
     return net
 
 
+# ---------------------------------------------------------------- fused training
+
+class FusableTraining(object):
+    """A module with a fused training path. _fused_training is a plain attribute (no state-dict key) that
+    fuse_training / unfuse_training set and clear; the path is taken only where _use_fused_training says so."""
+    _fused_training = False
+
+    def _use_fused_training(self, mlp, *tensors):
+        """Whether this forward runs its shared MLP on rows (rows_mlp): fuse_training was called, training mode,
+        float32 inputs on the GPU, and a stack whose layers are all 1x1 Conv + BatchNorm (training mode) + ReLU."""
+        if not (self._fused_training and self.training):
+            return False
+        if any(t is not None and (t.dtype != torch.float32 or not t.is_cuda) for t in tensors):
+            return False
+        return rows_stack(mlp)
+
+
+def rows_stack(mlp):
+    """True for a stack rows_mlp runs: every layer a bias-free 1x1 convolution, an affine BatchNorm in training mode
+    and a ReLU."""
+    if len(mlp) == 0:
+        return False
+    for m in mlp:
+        conv, bn = getattr(m, 'conv', None), getattr(m, 'bn', None)
+        if conv is None or bn is None or getattr(m, 'relu', None) is None:
+            return False
+        if any(k != 1 for k in conv.kernel_size) or any(s != 1 for s in conv.stride) \
+                or any(p != 0 for p in conv.padding) or conv.groups != 1 or conv.bias is not None:
+            return False
+        if not isinstance(bn, nn.modules.batchnorm._BatchNorm) or not bn.training or bn.weight is None \
+                or bn.bias is None:
+            return False
+    return True
+
+
+def rows_mlp(mlp, x, transposed, dropout=None):
+    """The shared MLP in training mode on rows, FeatureAggregation.forward_fused's loop: x (C, R) channel-major when
+    `transposed` (the first product reads it as a transposed operand), else (R, C) -> (R, out_channels). Per layer one
+    product on the f32 MFMA GEMM with BatchNorm's column statistics in its epilogue, then ops.bn_lrelu (BatchNorm over
+    the R rows -- the statistics of BatchNorm{1,2}d over (B, C, ...) -- and ReLU; running statistics and
+    num_batches_tracked are updated by the kernel). dropout: the probability of SharedMLPDO, applied to the rows."""
+    rows = x.shape[1] if transposed else x.shape[0]
+    n_valid = ops.row_count_for(rows)
+    if n_valid is None:
+        n_valid = ops.full_count(rows, x.device)
+    for layer in mlp:
+        w = layer.conv.weight
+        x = ops.linear(x, w.view(w.shape[0], w.shape[1]), x_is_transposed=transposed, stats_n_valid=n_valid)
+        x = ops.bn_lrelu(x, n_valid, layer.bn, 0.0)
+        transposed = False
+        if dropout is not None:
+            x = F.dropout(x, dropout, True)
+    return x
+
+
+def channel_rows(x):
+    """(B, C, N) -> (C, B*N) channel-major, the transposed operand of rows_mlp (one layout copy)."""
+    return x.transpose(0, 1).reshape(x.shape[1], -1).contiguous()
+
+
+def rows_to_channels(x, batch):
+    """(B*N, C) rows -> (B, C, N) contiguous (one layout copy)."""
+    return x.view(batch, -1, x.shape[1]).transpose(1, 2).contiguous()
+
+
+def fuse_training(net):
+    """Run the training-mode shared MLPs of every SetAbstraction, FeaturePropagation and PN2SSG under `net` (an MVPNet3D
+    is reached through its net_3d) on the library's GEMM and BatchNorm instead of Conv{1,2}d + BatchNorm{1,2}d. A
+    SetAbstraction with centroids is then its point search, ops.pn2_sa_rows (the rows of every ball-query group as one
+    channel-major operand: neither the grouped (B,C,M,K) tensor nor its concatenation with the coordinates is written),
+    per layer ops.linear + ops.bn_lrelu, and ops.pn2_rows_max; a FeaturePropagation with three neighbours and PN2SSG's
+    mlp_seg + seg_logit run the same layer loop on (B*N, C) rows. With ops.set_deterministic(True) such a training step
+    is bit-reproducible. Taken only in training mode, on float32 GPU inputs, for stacks of 1x1 Conv + BN +
+    ReLU; eval mode, the frozen path, num_centroids == 0, num_neighbors == 0, `lengths` and stacks without BatchNorm go
+    on as before. A plain attribute, not a buffer: state-dict keys stay as they are. Opt-in and off by default.
+    Returns net."""
+    for m in net.modules():
+        if isinstance(m, FusableTraining):
+            m._fused_training = True
+    return net
+
+
+def unfuse_training(net):
+    """Back to the PyTorch layers everywhere under `net`. Returns net."""
+    for m in net.modules():
+        if isinstance(m, FusableTraining):
+            m._fused_training = False
+    return net
+
+
 class QueryGrouper(nn.Module):
     """Ball query around every centroid, then the neighbours' coordinates (relative to the centroid) and features."""
 
@@ -150,7 +243,7 @@ class QueryGrouper(nn.Module):
         return _repr(self, ['radius', 'max_neighbors'])
 
 
-class SetAbstraction(Freezable, nn.Module):
+class SetAbstraction(Freezable, FusableTraining, nn.Module):
     """PointNet++ set abstraction: sample centroids, group, shared MLP, max over the neighbours.
     num_centroids: 0 = one group around the origin holding every point, -1 = every point is a centroid."""
 
@@ -196,9 +289,23 @@ class SetAbstraction(Freezable, nn.Module):
                 with torch.no_grad():
                     index = farthest_point_sample(xyz, self.num_centroids, lengths=lengths)
                 new_xyz = batch_index_select(xyz, index, dim=2)
+            if lengths is None and self._use_fused_training(self.mlp, xyz, feature):
+                return new_xyz, self._forward_rows(xyz, feature, new_xyz)
             group_feature, _ = self.grouper(new_xyz, xyz, feature, use_xyz=self.use_xyz, key_lengths=lengths)
         new_feature = self.mlp(group_feature)
         return new_xyz, torch.max(new_feature, dim=3)[0]
+
+    def _forward_rows(self, xyz, feature, new_xyz):
+        """The fused training path after the centroids are chosen (fuse_training): ball query, the group rows as one
+        channel-major operand, the shared MLP on rows, the max over each centroid's K rows -> (B,out_channels,M)."""
+        with torch.no_grad():
+            index = ball_query(new_xyz, xyz, self.radius, self.max_neighbors)
+        use_xyz = self.use_xyz or feature is None
+        # (coordinates that require a gradient are refused by the op: the rows carry none back to them)
+        x = ops.pn2_sa_rows(xyz.contiguous(), None if feature is None else feature.contiguous(), new_xyz.contiguous(),
+                            index, use_xyz=use_xyz)
+        x = rows_mlp(self.mlp, x, True)
+        return ops.pn2_rows_max(x, index.shape[0], index.shape[1], index.shape[2])
 
     def _snapshot(self):
         return None if self.num_centroids == 0 else fold_chain(self.mlp)
@@ -236,7 +343,7 @@ class FeatureInterpolator(nn.Module):
         return _repr(self, ['num_neighbors'])
 
 
-class FeaturePropagation(Freezable, nn.Module):
+class FeaturePropagation(Freezable, FusableTraining, nn.Module):
     """PointNet++ feature propagation: interpolate the sparse level's features onto the dense level (num_neighbors 3),
     or broadcast a single global feature (num_neighbors 0), then a shared MLP."""
 
@@ -266,4 +373,7 @@ class FeaturePropagation(Freezable, nn.Module):
             new_feature = torch.cat([sparse_feature.expand(-1, -1, dense_xyz.size(2)), dense_feature], dim=1)
         else:
             new_feature = self.interpolator(dense_xyz, sparse_xyz, dense_feature, sparse_feature)
+            if self._use_fused_training(self.mlp, new_feature):
+                # two layout copies of a (B,C,N1) tensor in torch around the rows (fuse_training)
+                return rows_to_channels(rows_mlp(self.mlp, channel_rows(new_feature), True), new_feature.shape[0])
         return self.mlp(new_feature)

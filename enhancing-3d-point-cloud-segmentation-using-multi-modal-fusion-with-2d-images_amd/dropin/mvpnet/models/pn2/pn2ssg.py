@@ -1,23 +1,26 @@
 """PointNet++ with single-scale grouping, the 3D network of the MVPNet baseline (reference
 mvpnet/models/pn2/pn2ssg.py; Qi et al., arXiv:1706.02413). Constructor arguments, defaults and sub-module names
 (sa_modules.N.mlp.M.conv, fp_modules, mlp_seg, seg_logit) are the reference's, so its checkpoints load.
-freeze_inference / unfreeze_inference (modules.py) switch the fused inference forward on and off."""
+freeze_inference / unfreeze_inference (modules.py) switch the fused inference forward on and off, fuse_training /
+unfuse_training the training-mode shared MLPs on the library's GEMM and BatchNorm."""
 import numpy as np
 import torch
 from torch import nn
 
 try:
     from ....common.nn import SharedMLPDO, xavier_uniform
-    from .modules import SetAbstraction, FeaturePropagation, Freezable, fold_chain, freeze_inference, unfreeze_inference
+    from .modules import (SetAbstraction, FeaturePropagation, Freezable, FusableTraining, fold_chain, freeze_inference,
+                          unfreeze_inference, fuse_training, unfuse_training, rows_mlp, channel_rows, rows_to_channels)
     from ...._native import ops
 except ImportError:
     from common.nn import SharedMLPDO, xavier_uniform
-    from mvpnet.models.pn2.modules import (SetAbstraction, FeaturePropagation, Freezable, fold_chain, freeze_inference,
-                                           unfreeze_inference)
+    from mvpnet.models.pn2.modules import (SetAbstraction, FeaturePropagation, Freezable, FusableTraining, fold_chain,
+                                           freeze_inference, unfreeze_inference, fuse_training, unfuse_training,
+                                           rows_mlp, channel_rows, rows_to_channels)
     from _native import ops
 
 
-class PN2SSG(Freezable, nn.Module):
+class PN2SSG(Freezable, FusableTraining, nn.Module):
     def __init__(self,
                  in_channels,
                  num_classes,
@@ -87,6 +90,14 @@ class PN2SSG(Freezable, nn.Module):
         frozen = self._use_frozen(up)
         if frozen is not None:      # mlp_seg + seg_logit in one launch; dropout is the identity in eval mode
             return {'seg_logit': ops.pn2_fp_mlp(None, None, None, up.contiguous(), *frozen, relu_last=False)}
+        if self.seg_logit.kernel_size == (1,) and self._use_fused_training(self.mlp_seg, up):
+            # mlp_seg on rows with its dropout, the logits as one more product plus the bias (fuse_training)
+            x = rows_mlp(self.mlp_seg, channel_rows(up), True, dropout=self.mlp_seg.p)
+            w = self.seg_logit.weight
+            x = ops.linear(x, w.view(w.shape[0], w.shape[1]))
+            if self.seg_logit.bias is not None:
+                x = x + self.seg_logit.bias
+            return {'seg_logit': rows_to_channels(x, up.shape[0])}
         return {'seg_logit': self.seg_logit(self.mlp_seg(up))}
 
     def _snapshot(self):

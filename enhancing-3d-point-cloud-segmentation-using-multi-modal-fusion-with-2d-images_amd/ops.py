@@ -2470,6 +2470,123 @@ def pn2_fa_mlp(feature_2d, image_xyz, points, index, params, widths, reduction='
 
 
 # --------------------------------------------------------------------------------------------
+# MVPNet baseline, training mode: group rows and the max over the neighbours (csrc/pn2_train.hip)
+# --------------------------------------------------------------------------------------------
+
+def _pn2_train_args(name, floats, index=None):
+    """The refusals shared by pn2_sa_rows and pn2_rows_max (dtype and layout first, then residence, like _pn2_mlp_args)."""
+    for t in floats:
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise RuntimeError("%s: floating operands must be float32 (got %s)" % (name, t.dtype))
+        if not t.is_contiguous():
+            raise RuntimeError("%s: operands must be contiguous" % name)
+    if index is not None:
+        if index.dtype != torch.int64:
+            raise RuntimeError("%s: index must be int64" % name)
+        if not index.is_contiguous():
+            raise RuntimeError("%s: operands must be contiguous" % name)
+    _dev(index, *floats)
+
+
+class _PN2SaRowsFn(torch.autograd.Function):
+    """X [Cin, B*M*K] of a ball-query group; the gradient goes to the features alone. The backward is a float-atomic
+    scatter-add by default; when set_deterministic was on in the forward it is the ordered gather over the transposed
+    index, the CSR kept under the CALLER's index tensor like _GroupPointsFn's (one CSR for both ops on one index)."""
+
+    @staticmethod
+    def forward(ctx, xyz, feature, new_xyz, index, use_xyz):
+        B, _, N = xyz.shape
+        M, K = index.shape[1], index.shape[2]
+        Cf = feature.shape[1] if feature is not None else 0
+        use_xyz = bool(use_xyz) or feature is None
+        X = torch.empty((Cf + (3 if use_xyz else 0), B * M * K), device=xyz.device, dtype=torch.float32)
+        check(lib().mvk_pn2_sa_rows_fwd(_p(xyz), _p(feature), _p(new_xyz), _p(index), B, Cf, int(use_xyz), N, M, K, _p(X),
+                                        _stream()))
+        ctx.save_for_backward(index)
+        ctx.dims = (B, Cf, N, M, K)
+        ctx.det, ctx.csr_owner = is_deterministic(), index
+        return X
+
+    @staticmethod
+    def backward(ctx, grad_x):
+        (index,) = ctx.saved_tensors
+        B, Cf, N, M, K = ctx.dims
+        if Cf == 0 or not ctx.needs_input_grad[1]:
+            return None, None, None, None, None
+        g = _f32c(grad_x)
+        if ctx.det:
+            row_start, entries = _index_csr_shared(ctx.csr_owner, index, N)
+            gf = torch.empty((B, Cf, N), device=g.device, dtype=torch.float32)          # every element is written
+            check(lib().mvk_pn2_sa_rows_bwd_csr(_p(g), _p(row_start), _p(entries), B, Cf, N, M, K, _p(gf), _stream()))
+            return None, gf, None, None, None
+        gf = torch.zeros((B, Cf, N), device=g.device, dtype=torch.float32)
+        check(lib().mvk_pn2_sa_rows_bwd(_p(g), _p(index), B, Cf, N, M, K, _p(gf), _stream()))
+        return None, gf, None, None, None
+
+
+def pn2_sa_rows(xyz, feature, new_xyz, index, use_xyz=True):
+    """The input rows of a SetAbstraction's shared MLP after its ball query, as the transposed operand of ops.linear:
+    xyz (B,3,N), feature (B,C,N) or None, new_xyz (B,3,M), index (B,M,K) int64 -> X (Cin, B*M*K) channel-major, column
+    (b*M + m)*K + k = [feature[b, :, j] | xyz[b, :, j] - new_xyz[b, :, m]] with j = index[b, m, k] (QueryGrouper's order);
+    the coordinates alone without features, the features alone with use_xyz False. An index outside [0, N) reads as zero
+    before the centroid is subtracted, like group_points. Differentiable in `feature` only (atomic scatter-add, or the
+    ordered per-key sums when set_deterministic was on in the forward); coordinates that require a gradient are refused.
+    One launch, no host synchronisation."""
+    _pn2_train_args("pn2_sa_rows", (xyz, feature, new_xyz), index)
+    if xyz.dim() != 3 or xyz.shape[1] != 3 or new_xyz.dim() != 3 or new_xyz.shape[1] != 3 or index.dim() != 3 \
+            or new_xyz.shape[0] != xyz.shape[0] or tuple(index.shape[:2]) != (xyz.shape[0], new_xyz.shape[2]) \
+            or (feature is not None and (feature.dim() != 3 or feature.shape[0] != xyz.shape[0]
+                                         or feature.shape[2] != xyz.shape[2])):
+        raise RuntimeError("pn2_sa_rows: expected xyz (B,3,N), feature (B,C,N) or None, new_xyz (B,3,M), index (B,M,K)")
+    if torch.is_grad_enabled() and (xyz.requires_grad or new_xyz.requires_grad):
+        raise RuntimeError("pn2_sa_rows has no gradient for coordinates: pass xyz and new_xyz detached")
+    if index.numel() >= 1 << 31:
+        raise RuntimeError("pn2_sa_rows: B*M*K = %d rows must be below 2^31" % index.numel())
+    return _PN2SaRowsFn.apply(xyz, feature, new_xyz, index, use_xyz)
+
+
+class _PN2RowsMaxFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, B, M, K):
+        Cout = y.shape[1]
+        out = torch.empty((B, Cout, M), device=y.device, dtype=torch.float32)
+        arg = torch.empty((B, Cout, M), device=y.device, dtype=torch.int32)
+        check(lib().mvk_pn2_rows_max_fwd(_p(y), B, M, K, Cout, _p(out), _p(arg), _stream()))
+        ctx.save_for_backward(arg)
+        ctx.dims = (B, M, K, Cout)
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, g, _g_arg=None):
+        (arg,) = ctx.saved_tensors
+        B, M, K, Cout = ctx.dims
+        g = _f32c(g)
+        dy = torch.empty((B * M * K, Cout), device=g.device, dtype=torch.float32)       # every element is written
+        check(lib().mvk_pn2_rows_max_bwd(_p(g), _p(arg), B, M, K, Cout, _p(dy), _stream()))
+        return dy, None, None, None
+
+
+def pn2_rows_max(y, B, M, K, return_arg=False):
+    """The max over the neighbours on rows: y (B*M*K, Cout) row-major, row (b*M + m)*K + k (what ops.bn_lrelu returns)
+    -> (B, Cout, M), the layout the next level reads. Among equal maxima the smallest k is the one that receives the
+    gradient (a ball query pads its rows with copies of the first hit); a NaN propagates as in torch.max. return_arg:
+    also that k, int32 (B, Cout, M). One launch forward, one backward (every element of the gradient is written: no zero
+    fill, no atomics)."""
+    _pn2_train_args("pn2_rows_max", (y,))
+    B, M, K = int(B), int(M), int(K)
+    if y.dim() != 2 or B < 0 or M < 0 or K < 1 or y.shape[0] != B * M * K:
+        raise RuntimeError("pn2_rows_max: expected y (B*M*K, Cout) with K >= 1, got %s for B=%d M=%d K=%d"
+                           % (tuple(y.shape), B, M, K))
+    if y.shape[0] >= 1 << 31:
+        raise RuntimeError("pn2_rows_max: B*M*K = %d rows must be below 2^31" % y.shape[0])
+    out, arg = _PN2RowsMaxFn.apply(y, B, M, K)
+    return (out, arg) if return_arg else out
+
+
+# --------------------------------------------------------------------------------------------
 # fused FeatureAggregation path: gather kernel + MFMA linear layers
 # --------------------------------------------------------------------------------------------
 

@@ -124,7 +124,9 @@ int mvk_gemm_f32(const float* A, const float* B, float* C, int64_t M, int64_t N,
  * per block of `rows` rows and column, the sum and the sum of squares about the block's own mean over the rows
  * below *n_valid (DEVICE int32; NULL = M); `rows` and the split the call will use come from mvk_gemm_f32_plan
  * for the same (M, N, Kd, split_k, want_stats = bn_part != NULL). The caller zeroes C when the plan's split
- * is > 1; statistics are only produced by unsplit plans (plan: *out_stat_rows > 0). */
+ * is > 1; statistics are only produced by unsplit plans (plan: *out_stat_rows > 0).
+ * A product of 2^16 row tiles or more (from 2^20 rows on, depending on the plan's tile) runs as row chunks of 15 * 2^16
+ * rows, one launch each with the plan's split; bn_part must then be NULL (refused otherwise). */
 int mvk_gemm_f32_plan(int64_t M, int64_t N, int64_t Kd, int split_k, int want_stats, int* out_split,
                       int* out_stat_rows);
 int mvk_gemm_f32_ex(const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t Kd, int transA,
@@ -843,6 +845,38 @@ int mvk_group_points_bwd_csr(const float* grad_out, const int32_t* row_start, co
                              int64_t N1, int64_t N2, int K, float* grad_in, void* stream);
 int mvk_group_points_bwd_csr_f64(const double* grad_out, const int32_t* row_start, const int32_t* entries, int B, int C,
                                  int64_t N1, int64_t N2, int K, double* grad_in, void* stream);
+
+/* ---------------- PointNet++ set abstraction in training mode (csrc/pn2_train.hip) ------------------------- */
+/* The two ends of a SetAbstraction's shared MLP when its products run on mvk_gemm_f32 and its BatchNorm on
+ * mvk_bn_lrelu_*: the operand rows of a ball-query group and the maximum over a centroid's K rows, each with its
+ * backward. R = B*M*K rows, row r = (b*M + m)*K + k; R must be below 2^31 (refused otherwise). One launch each, no host
+ * synchronisation, no workspace: capturable.
+ *
+ * mvk_pn2_sa_rows_fwd: xyz [B,3,N], feature [B,C,N] or NULL, new_xyz [B,3,M], index [B,M,K] int64 -> X [Cin,R]
+ * channel-major (the transposed operand of the first product), column r = [feature[b,:,j] | xyz[b,:,j] - new_xyz[b,:,m]],
+ * j = index[b,m,k]; Cin = C + 3 with use_xyz != 0, C otherwise, 3 when feature is NULL (C and use_xyz are then ignored).
+ * An index outside [0, N) reads as zero for the features and for xyz BEFORE the centroid is subtracted (the contract of
+ * mvk_pn2_sa_fwd). The subtraction is one float32 rounding.
+ * mvk_pn2_sa_rows_bwd: dX [Cin,R] -> dfeature [B,C,N] += dX[c,r] at j = index of r, by float atomics: the caller zeroes
+ * dfeature. Rows C.. of dX (the coordinates) are not read: coordinates get no gradient. An index outside [0, N) adds
+ * nothing.
+ * mvk_pn2_sa_rows_bwd_csr: the same sums in a fixed order. row_start / entries: mvk_index_csr of the forward's index
+ * with the same B, N1 = N and L = M*K. dfeature[b,c,j]: acc = 0; for p in row (b, j), ascending: acc = fl(acc +
+ * dX[c, b*L + p]); every element is written (+0 for a key without entries, no zero fill by the caller); a row of any
+ * length is one lane's loop. */
+int mvk_pn2_sa_rows_fwd(const float* xyz, const float* feature, const float* new_xyz, const int64_t* index, int B, int C,
+                        int use_xyz, int64_t N, int64_t M, int K, float* X, void* stream);
+int mvk_pn2_sa_rows_bwd(const float* dX, const int64_t* index, int B, int C, int64_t N, int64_t M, int K, float* dfeature,
+                        void* stream);
+int mvk_pn2_sa_rows_bwd_csr(const float* dX, const int32_t* row_start, const int32_t* entries, int B, int C, int64_t N,
+                            int64_t M, int K, float* dfeature, void* stream);
+/* mvk_pn2_rows_max_fwd: Y [R,Cout] row-major -> out [B,Cout,M] float32 = max over k of Y[(b*M + m)*K + k, c] and arg
+ * [B,Cout,M] int32 = the SMALLEST k attaining it (ball-query rows are padded with copies of the first hit: equal maxima
+ * are the normal case). A NaN in a group propagates (arg = the first NaN), as in torch.max. K >= 1.
+ * mvk_pn2_rows_max_bwd: g [B,Cout,M], arg -> dY [R,Cout], every element written: g at k == arg, +0 elsewhere (an arg
+ * outside [0, K) leaves the group at +0). No zero fill, no atomics. */
+int mvk_pn2_rows_max_fwd(const float* Y, int B, int64_t M, int K, int Cout, float* out, int32_t* arg, void* stream);
+int mvk_pn2_rows_max_bwd(const float* g, const int32_t* arg, int B, int64_t M, int K, int Cout, float* dY, void* stream);
 
 /* ---------------- MVPNet whole-scene test: chunks, logit votes, confusion (csrc/chunk.hip) ------------------------- */
 
