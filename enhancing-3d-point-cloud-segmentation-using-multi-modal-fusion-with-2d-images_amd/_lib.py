@@ -195,6 +195,11 @@ _SIGNATURES = {
     "mvk_pn2_sa_rows_bwd_csr": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _i, _vp, _vp]),
     "mvk_pn2_rows_max_fwd": (C.c_int, [_vp, _i, _i64, _i, _i, _vp, _vp, _vp]),
     "mvk_pn2_rows_max_bwd": (C.c_int, [_vp, _vp, _i, _i64, _i, _i, _vp, _vp]),
+    "mvk_pn2_fa_rows_fwd": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _i, _i, _vp, _vp]),
+    "mvk_pn2_fa_rows_bwd": (C.c_int, [_vp, _vp, _i, _i, _i, _i64, _i64, _i, _vp, _i64, _i64, _i64, _vp]),
+    "mvk_pn2_fa_rows_bwd_csr": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i64, _i64, _i, _vp, _i64, _i64, _i64, _vp]),
+    "mvk_pn2_rows_sum_fwd": (C.c_int, [_vp, _i, _i64, _i, _i, _vp, _vp]),
+    "mvk_pn2_rows_sum_bwd": (C.c_int, [_vp, _i, _i64, _i, _i, _vp, _vp]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

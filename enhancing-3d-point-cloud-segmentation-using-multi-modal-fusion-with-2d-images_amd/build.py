@@ -35,6 +35,7 @@ SOURCES = [
     ("pn2_ordered.hip", ["-ffp-contract=off"]),   # ordered backwards: a product and its addition are two roundings
     ("pn2_mlp.hip", ["-ffp-contract=off"]),   # its 3-NN interpolation is pn2.hip's bit for bit; the products are MFMAs either way
     ("pn2_train.hip", ["-ffp-contract=off"]),     # group rows: xyz - centroid in one rounding; ordered sums without FMA
+    ("fa_train.hip", ["-ffp-contract=off"]),      # aggregation rows: difference and squared distance as torch rounds them; ordered sums
 ]
 
 

@@ -4,7 +4,9 @@ Sub-module names (mlp.{i}.conv / mlp.{i}.bn) match the reference so MVPNet check
 MVPNet3D (reference :73-135): the baseline's wiring 2D encoder -> unprojection by group_points ->
 FeatureAggregation -> 3D network (PN2SSG). After freeze_inference(net, aggregation=True) (pn2/modules.py) the
 unprojection and the aggregation of an eval-mode forward under torch.no_grad() are ONE fused launch on the encoder's
-map (ops.pn2_fa_mlp, csrc/pn2_mlp.hip)."""
+map (ops.pn2_fa_mlp, csrc/pn2_mlp.hip). After fuse_training(net, aggregation=True) a training-mode forward runs them on
+that map through ops.pn2_fa_rows, the library's GEMM and BatchNorm and ops.pn2_rows_sum / pn2_rows_max
+(csrc/fa_train.hip), with the map's gradient written in the map's own memory format."""
 import logging
 
 import numpy as np
@@ -18,14 +20,17 @@ try:
 except ImportError:
     from common.nn import SharedMLP, xavier_uniform
     from _native import ops
-from .pn2.modules import Freezable, fold_chain
+from .pn2.modules import Freezable, FusableTraining, fold_chain, rows_mlp
 
 
-class FeatureAggregation(Freezable, nn.Module):
+class FeatureAggregation(Freezable, FusableTraining, nn.Module):
     """Feature Aggregation inspired by ContFuse. After freeze_inference(net, aggregation=True) it holds a snapshot
     (params, widths, reduction name, use_relation) -- a plain attribute, no state-dict key, dropped by train(True) --
-    and from_encoder_map runs the whole module, grouping included, as one fused launch."""
+    and from_encoder_map runs the whole module, grouping included, as one fused launch. After
+    fuse_training(net, aggregation=True) forward_rows runs it in training mode for a batch, grouping included, on the
+    library's row builder, GEMM, BatchNorm and reduction (csrc/fa_train.hip)."""
     _freeze_on_request = True
+    _fuse_on_request = True
 
     def __init__(self, in_channels, mlp_channels=(64, 64, 64), reduction='sum', use_relation=True):
         super(FeatureAggregation, self).__init__()
@@ -62,6 +67,34 @@ class FeatureAggregation(Freezable, nn.Module):
             feature_2d = feature_2d.contiguous()
         return ops.pn2_fa_mlp(feature_2d, image_xyz.contiguous(), points.contiguous(), knn_indices.contiguous(), params,
                               widths, reduction=reduction, use_relation=use_relation, lengths=lengths)
+
+    def _use_rows(self, feature_2d, image_xyz, points):
+        """Whether a training-mode batch takes forward_rows: fuse_training(net, aggregation=True) was called, training
+        mode, float32 GPU inputs, an MLP of 1x1 Conv + BatchNorm + ReLU layers, sum or max over k."""
+        if self.mlp is None or self._reduction_name is None:
+            return False
+        return self._use_fused_training(self.mlp, feature_2d, image_xyz, points)
+
+    def forward_rows(self, feature_2d, image_xyz, knn_indices, points):
+        """The module in training mode on the encoder's output as it lies (fuse_training(net, aggregation=True)):
+        feature_2d (b*nv,c,h,w) contiguous or channels-last, image_xyz (b,nv,h,w,3), knn_indices (b,np,k) int64 flat
+        pixel indices, points (b,3,np) -> (b,out,np), what forward() gives on the two group_points results. The rows of
+        every (point, pixel) pair as one channel-major operand (ops.pn2_fa_rows: no transposed copy of the map, no
+        grouped tensor, no concatenation), the shared MLP on rows (ops.linear + ops.bn_lrelu, BatchNorm over the
+        b*np*k rows: BatchNorm2d's statistics over (b,C,np,k)), then the sum or max over each point's k rows. The
+        gradient reaches feature_2d alone, in its memory format."""
+        if self.mlp is None or self._reduction_name is None:
+            raise RuntimeError("forward_rows needs an MLP and a sum or max reduction")
+        if not (feature_2d.is_contiguous() or feature_2d.is_contiguous(memory_format=torch.channels_last)):
+            feature_2d = feature_2d.contiguous()
+        index = knn_indices if knn_indices.is_contiguous() else knn_indices.contiguous()
+        x = ops.pn2_fa_rows(feature_2d, image_xyz.contiguous(), points.contiguous(), index,
+                            use_relation=bool(self.use_relation))
+        x = rows_mlp(self.mlp, x, True)
+        b, n_pts, k = index.shape
+        if self._reduction_name == 'sum':
+            return ops.pn2_rows_sum(x, b, n_pts, k)
+        return ops.pn2_rows_max(x, b, n_pts, k)
 
     def forward(self, src_xyz, tgt_xyz, feature):
         """src_xyz (b,3,np,k), tgt_xyz (b,3,np), feature (b,c,np,k) -> (b,out,np)."""
@@ -153,6 +186,14 @@ class MVPNet3D(nn.Module):
             if lengths is not None:
                 batch_3d['lengths'] = lengths
             return self.net_3d(batch_3d)
+        if data_batch.get('lengths', None) is None \
+                and self.feat_aggreg._use_rows(feature_2d, data_batch['image_xyz'], data_batch['points']):
+            # the hand-off in training mode on the encoder's map (fuse_training(net, aggregation=True)); BatchNorm over
+            # the padded rows of a `lengths` batch would be another function, so that case goes on below
+            points = data_batch['points']
+            return self.net_3d({'points': points,
+                                'feature': self.feat_aggreg.forward_rows(feature_2d, data_batch['image_xyz'],
+                                                                         knn_indices, points)})
         feature_2d = feature_2d.reshape(b, nv, -1, h, w).transpose(1, 2).contiguous().reshape(b, -1, nv * h * w)
         feature_2d = ops.group_points(feature_2d, knn_indices)                     # (b, c, np, k)
         with torch.no_grad():

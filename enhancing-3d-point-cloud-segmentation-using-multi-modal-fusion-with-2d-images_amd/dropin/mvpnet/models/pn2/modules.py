@@ -131,8 +131,11 @@ def unfreeze_inference(net):
 
 class FusableTraining(object):
     """A module with a fused training path. _fused_training is a plain attribute (no state-dict key) that
-    fuse_training / unfuse_training set and clear; the path is taken only where _use_fused_training says so."""
+    fuse_training / unfuse_training set and clear; the path is taken only where _use_fused_training says so.
+    _fuse_on_request: fuse_training sets the attribute only when asked to by name (FeatureAggregation:
+    aggregation=True)."""
     _fused_training = False
+    _fuse_on_request = False
 
     def _use_fused_training(self, mlp, *tensors):
         """Whether this forward runs its shared MLP on rows (rows_mlp): fuse_training was called, training mode,
@@ -192,7 +195,7 @@ def rows_to_channels(x, batch):
     return x.view(batch, -1, x.shape[1]).transpose(1, 2).contiguous()
 
 
-def fuse_training(net):
+def fuse_training(net, aggregation=False):
     """Run the training-mode shared MLPs of every SetAbstraction, FeaturePropagation and PN2SSG under `net` (an MVPNet3D
     is reached through its net_3d) on the library's GEMM and BatchNorm instead of Conv{1,2}d + BatchNorm{1,2}d. A
     SetAbstraction with centroids is then its point search, ops.pn2_sa_rows (the rows of every ball-query group as one
@@ -202,9 +205,17 @@ def fuse_training(net):
     is bit-reproducible. Taken only in training mode, on float32 GPU inputs, for stacks of 1x1 Conv + BN +
     ReLU; eval mode, the frozen path, num_centroids == 0, num_neighbors == 0, `lengths` and stacks without BatchNorm go
     on as before. A plain attribute, not a buffer: state-dict keys stay as they are. Opt-in and off by default.
-    Returns net."""
+
+    aggregation=True additionally switches every FeatureAggregation under `net` (an MVPNet3D's feat_aggreg), mirroring
+    freeze_inference(net, aggregation=True): a training-mode MVPNet3D.forward then goes from the 2D encoder's map to the
+    3D network's input features through ops.pn2_fa_rows (the rows of every point's k pixels as one channel-major
+    operand, read from the map in place, NCHW or channels-last, with the gradient written back in that format), per
+    layer ops.linear + ops.bn_lrelu, and ops.pn2_rows_sum or ops.pn2_rows_max -- no transposed copy of the map, no
+    group_points, no concatenation, no Conv2d / BatchNorm2d forward. With ops.set_deterministic(True) everything after
+    the 2D encoder is then bit-reproducible. A batch with `lengths`, a module without an MLP and a reduction other
+    than sum or max go on as before; the default leaves FeatureAggregation modules exactly as they are. Returns net."""
     for m in net.modules():
-        if isinstance(m, FusableTraining):
+        if isinstance(m, FusableTraining) and (aggregation or not m._fuse_on_request):
             m._fused_training = True
     return net
 

@@ -2587,6 +2587,117 @@ def pn2_rows_max(y, B, M, K, return_arg=False):
 
 
 # --------------------------------------------------------------------------------------------
+# MVPNet baseline, training mode: the 2D -> 3D hand-off around FeatureAggregation's shared MLP (csrc/fa_train.hip,
+# DESIGN 7o)
+# --------------------------------------------------------------------------------------------
+
+class _PN2FaRowsFn(torch.autograd.Function):
+    """X [C (+4), B*N*K] of a batch of aggregation rows; the gradient goes to the encoder's map alone, in the map's own
+    memory format. Atomic scatter-add by default; when set_deterministic was on in the forward, the ordered gather over
+    the transposed index with nv*h*w keys, the CSR kept under the CALLER's index tensor like _GroupPointsFn's."""
+
+    @staticmethod
+    def forward(ctx, feature_2d, image_xyz, points, index, use_relation):
+        B, nv, h, w = image_xyz.shape[:4]
+        Cf, N, K = feature_2d.shape[1], points.shape[2], index.shape[2]
+        hw = h * w
+        channels_last = not feature_2d.is_contiguous()
+        strides = (Cf * hw, 1, Cf) if channels_last else (Cf * hw, hw, 1)
+        X = torch.empty((Cf + (4 if use_relation else 0), B * N * K), device=points.device, dtype=torch.float32)
+        check(lib().mvk_pn2_fa_rows_fwd(_p(feature_2d), strides[0], strides[1], strides[2], _p(image_xyz), _p(points),
+                                        _p(index), B, nv, Cf, hw, N, K, int(use_relation), _p(X), _stream()))
+        ctx.save_for_backward(index)
+        ctx.dims, ctx.strides, ctx.channels_last = (B, nv, Cf, h, w, N, K), strides, channels_last
+        ctx.det, ctx.csr_owner = is_deterministic(), index
+        return X
+
+    @staticmethod
+    def backward(ctx, grad_x):
+        (index,) = ctx.saved_tensors
+        B, nv, Cf, h, w, N, K = ctx.dims
+        if Cf == 0 or not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        g = _f32c(grad_x)
+        fmt = torch.channels_last if ctx.channels_last else torch.contiguous_format
+        si, sc, sp = ctx.strides
+        if ctx.det:
+            row_start, entries = _index_csr_shared(ctx.csr_owner, index, nv * h * w)
+            gm = torch.empty((B * nv, Cf, h, w), device=g.device, dtype=torch.float32, memory_format=fmt)   # all written
+            check(lib().mvk_pn2_fa_rows_bwd_csr(_p(g), _p(row_start), _p(entries), B, nv, Cf, h * w, N, K, _p(gm), si, sc,
+                                                sp, _stream()))
+            return gm, None, None, None, None
+        gm = torch.empty((B * nv, Cf, h, w), device=g.device, dtype=torch.float32, memory_format=fmt).zero_()
+        check(lib().mvk_pn2_fa_rows_bwd(_p(g), _p(index), B, nv, Cf, h * w, N, K, _p(gm), si, sc, sp, _stream()))
+        return gm, None, None, None, None
+
+
+def pn2_fa_rows(feature_2d, image_xyz, points, index, use_relation=True):
+    """The input rows of FeatureAggregation's shared MLP for a batch, straight from the 2D encoder's map, as the
+    transposed operand of ops.linear: feature_2d (B*nv,C,h,w), contiguous or channels-last and read in place, image_xyz
+    (B,nv,h,w,3), points (B,3,N), index (B,N,K) int64 flat pixel indices view*h*w + pixel -> X (C+4, B*N*K)
+    channel-major, column (b*N + n)*K + k = [feature_2d at the pixel | image_xyz at the pixel - point | squared
+    distance]; the features alone, (C, B*N*K), with use_relation False. An index outside [0, nv*h*w) reads as zero before
+    the point is subtracted, like the two group_points calls of MVPNet3D.forward. Differentiable in feature_2d only
+    (atomic scatter-add, or the ordered per-pixel sums when set_deterministic was on in the forward; the gradient has the
+    map's memory format); image_xyz or points that require a gradient are refused. One launch, no host synchronisation."""
+    name = "pn2_fa_rows"
+    if feature_2d.dtype != torch.float32:
+        raise RuntimeError("%s: floating operands must be float32 (got %s)" % (name, feature_2d.dtype))
+    if feature_2d.dim() != 4:
+        raise RuntimeError("%s: expected feature_2d (B*nv,C,h,w)" % name)
+    if not (feature_2d.is_contiguous() or feature_2d.is_contiguous(memory_format=torch.channels_last)):
+        raise RuntimeError("%s: feature_2d must be contiguous or channels-last" % name)
+    _pn2_train_args(name, (image_xyz, points), index)
+    _dev(feature_2d)
+    if image_xyz.dim() != 5 or image_xyz.shape[4] != 3 or points.dim() != 3 or points.shape[1] != 3 or index.dim() != 3 \
+            or points.shape[0] != image_xyz.shape[0] or tuple(index.shape[:2]) != (points.shape[0], points.shape[2]) \
+            or tuple(image_xyz.shape[2:4]) != tuple(feature_2d.shape[2:]):
+        raise RuntimeError("%s: expected feature_2d (B*nv,C,h,w), image_xyz (B,nv,h,w,3), points (B,3,N), index (B,N,K)"
+                           % name)
+    B, nv, h, w = image_xyz.shape[:4]
+    if feature_2d.shape[0] != B * nv:
+        raise RuntimeError("%s: feature_2d holds %d images, image_xyz has %d x %d views" % (name, feature_2d.shape[0], B, nv))
+    if torch.is_grad_enabled() and (image_xyz.requires_grad or points.requires_grad):
+        raise RuntimeError("%s has no gradient for coordinates: pass image_xyz and points detached" % name)
+    if index.numel() >= 1 << 31 or B * nv * h * w >= 1 << 31:
+        raise RuntimeError("%s: B*N*K = %d rows and B*nv*h*w = %d pixels must be below 2^31"
+                           % (name, index.numel(), B * nv * h * w))
+    return _PN2FaRowsFn.apply(feature_2d, image_xyz, points, index, bool(use_relation))
+
+
+class _PN2RowsSumFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, B, M, K):
+        Cout = y.shape[1]
+        out = torch.empty((B, Cout, M), device=y.device, dtype=torch.float32)
+        check(lib().mvk_pn2_rows_sum_fwd(_p(y), B, M, K, Cout, _p(out), _stream()))
+        ctx.dims = (B, M, K, Cout)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        B, M, K, Cout = ctx.dims
+        g = _f32c(g)
+        dy = torch.empty((B * M * K, Cout), device=g.device, dtype=torch.float32)       # every element is written
+        check(lib().mvk_pn2_rows_sum_bwd(_p(g), B, M, K, Cout, _p(dy), _stream()))
+        return dy, None, None, None
+
+
+def pn2_rows_sum(y, B, M, K):
+    """The sum over the neighbours on rows: y (B*M*K, Cout) row-major, row (b*M + m)*K + k (what ops.bn_lrelu returns)
+    -> (B, Cout, M): the first row's value, then one rounded float32 addition per further row in ascending k. One launch
+    forward, one backward (every element of the gradient is written: no zero fill, no atomics)."""
+    _pn2_train_args("pn2_rows_sum", (y,))
+    B, M, K = int(B), int(M), int(K)
+    if y.dim() != 2 or B < 0 or M < 0 or K < 1 or y.shape[0] != B * M * K:
+        raise RuntimeError("pn2_rows_sum: expected y (B*M*K, Cout) with K >= 1, got %s for B=%d M=%d K=%d"
+                           % (tuple(y.shape), B, M, K))
+    if y.shape[0] >= 1 << 31:
+        raise RuntimeError("pn2_rows_sum: B*M*K = %d rows must be below 2^31" % y.shape[0])
+    return _PN2RowsSumFn.apply(y, B, M, K)
+
+
+# --------------------------------------------------------------------------------------------
 # fused FeatureAggregation path: gather kernel + MFMA linear layers
 # --------------------------------------------------------------------------------------------
 

@@ -24,6 +24,8 @@
  *   mvk_box_*, mvk_chunk_*    mvpnet/utils/chunk_util.py:4-53, mvpnet/test_mvpnet_3d.py:141-178,
  *                             mvpnet/evaluate_3d.py:19-36 (the MVPNet baseline's whole-scene test; added under ABI 9,
  *                             nothing older changed)
+ *   mvk_pn2_fa_rows_*, mvk_pn2_rows_sum_*  mvpnet/models/mvpnet_3d.py:110-125, :40-49 in training mode (the 2D -> 3D
+ *                             hand-off around FeatureAggregation's shared MLP; added under ABI 9, nothing older changed)
  */
 #ifndef MVKPCONV_H
 #define MVKPCONV_H
@@ -877,6 +879,43 @@ int mvk_pn2_sa_rows_bwd_csr(const float* dX, const int32_t* row_start, const int
  * outside [0, K) leaves the group at +0). No zero fill, no atomics. */
 int mvk_pn2_rows_max_fwd(const float* Y, int B, int64_t M, int K, int Cout, float* out, int32_t* arg, void* stream);
 int mvk_pn2_rows_max_bwd(const float* g, const int32_t* arg, int B, int64_t M, int K, int Cout, float* dY, void* stream);
+
+/* ---------------- MVPNet's 2D -> 3D hand-off in training mode (csrc/fa_train.hip) ------------------------- */
+/* The two ends of FeatureAggregation's shared MLP for a whole batch when its products run on mvk_gemm_f32 and its
+ * BatchNorm on mvk_bn_lrelu_*. feature_2d, its three element strides, image_xyz [B, nv * HW, 3], points [B,3,N] and
+ * index [B,N,K] (int64 flat pixel indices j = view * HW + pixel in [0, P), P = nv * HW) are those of mvk_pn2_fa_fwd: the
+ * map is read, and its gradient written, in place, NCHW or channels-last. R = B*N*K rows, row r = (b*N + n)*K + k;
+ * R >= 2^31 and B*P >= 2^31 are refused. One launch each, no host synchronisation, no workspace: capturable; an empty
+ * problem launches nothing.
+ *
+ * mvk_pn2_fa_rows_fwd: -> X [C + 4, R] channel-major (the transposed operand of the first product; [C, R] with
+ * use_relation == 0), column r = [feature_2d(b * nv + j / HW, c, j % HW) for c < C | d_0..2 | (d_0*d_0 + d_1*d_1) +
+ * d_2*d_2], d = image_xyz[b, j] - points[b, :, n], every operation one float32 rounding (no FMA). An index outside
+ * [0, P) reads as zero for the features and for image_xyz BEFORE the point is subtracted (mvk_pn2_sa_rows_fwd's contract,
+ * what two group_points calls give; not mvk_fa_gather_fwd's all-zero row).
+ * mvk_pn2_fa_rows_bwd: dX [.., R] -> dfeature_2d (the map's shape, addressed with the same three strides) += dX[c, r]
+ * at the pixel of r, by float atomics: the caller zeroes dfeature_2d. Rows C.. of dX are not read: image_xyz and points
+ * get no gradient. An index outside [0, P) adds nothing.
+ * mvk_pn2_fa_rows_bwd_csr: the same sums in a fixed order. row_start / entries: mvk_index_csr of the forward's index with
+ * the same B, N1 = P and L = N*K. Per element of the map: acc = 0; for p in row (b, j), ascending: acc = fl(acc +
+ * dX[c, b*L + p]); every element is written (+0 for a pixel without entries, no zero fill by the caller); a row of any
+ * length is one lane's loop. */
+int mvk_pn2_fa_rows_fwd(const float* feature_2d, int64_t stride_image, int64_t stride_channel, int64_t stride_pixel,
+                        const float* image_xyz, const float* points, const int64_t* index, int B, int nv, int C,
+                        int64_t HW, int64_t N, int K, int use_relation, float* X, void* stream);
+int mvk_pn2_fa_rows_bwd(const float* dX, const int64_t* index, int B, int nv, int C, int64_t HW, int64_t N, int K,
+                        float* dfeature_2d, int64_t stride_image, int64_t stride_channel, int64_t stride_pixel,
+                        void* stream);
+int mvk_pn2_fa_rows_bwd_csr(const float* dX, const int32_t* row_start, const int32_t* entries, int B, int nv, int C,
+                            int64_t HW, int64_t N, int K, float* dfeature_2d, int64_t stride_image,
+                            int64_t stride_channel, int64_t stride_pixel, void* stream);
+/* mvk_pn2_rows_sum_fwd: Y [R,Cout] row-major, R = B*M*K -> out [B,Cout,M]: acc = Y[(b*M + m)*K, c], then acc = fl(acc +
+ * Y[(b*M + m)*K + k, c]) for k = 1 .. K-1 in that order (K = 1 is a copy; -0, infinities and NaN as float32 addition
+ * gives them). K >= 1.
+ * mvk_pn2_rows_sum_bwd: g [B,Cout,M] -> dY [R,Cout], every element written (g[b,c,m] in each of the K rows). No zero
+ * fill, no atomics. The max over the K rows is mvk_pn2_rows_max_*. */
+int mvk_pn2_rows_sum_fwd(const float* Y, int B, int64_t M, int K, int Cout, float* out, void* stream);
+int mvk_pn2_rows_sum_bwd(const float* g, int B, int64_t M, int K, int Cout, float* dY, void* stream);
 
 /* ---------------- MVPNet whole-scene test: chunks, logit votes, confusion (csrc/chunk.hip) ------------------------- */
 
