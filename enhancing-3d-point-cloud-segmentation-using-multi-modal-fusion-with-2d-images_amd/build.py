@@ -34,8 +34,7 @@ SOURCES = [
     ("chunk.hip", ["-ffp-contract=off"]),     # float64 box tests, float32 vote sums and division as NumPy evaluates them
     ("pn2_ordered.hip", ["-ffp-contract=off"]),   # ordered backwards: a product and its addition are two roundings
     ("pn2_mlp.hip", ["-ffp-contract=off"]),   # its 3-NN interpolation is pn2.hip's bit for bit; the products are MFMAs either way
-    ("pn2_train.hip", ["-ffp-contract=off"]),     # group rows: xyz - centroid in one rounding; ordered sums without FMA
-    ("fa_train.hip", ["-ffp-contract=off"]),      # aggregation rows: difference and squared distance as torch rounds them; ordered sums
+    ("pn2_rows.hip", ["-ffp-contract=off"]),      # group / aggregation rows: differences and squared distance as torch rounds them
 ]
 
 
@@ -56,6 +55,7 @@ def _stale(target, deps):
 def build_library(force=False, verbose=False):
     hipcc = _hipcc()
     common = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "blockscan.h"), os.path.join(CSRC, "compact.h"),
+              os.path.join(CSRC, "pn2_rows.h"),
               os.path.join(HERE, "..", "include", "mvkpconv.h"),
               os.path.join(HERE, "..", "include", "mvk_prime_list.h"), os.path.abspath(__file__)]
     objs, jobs = [], []

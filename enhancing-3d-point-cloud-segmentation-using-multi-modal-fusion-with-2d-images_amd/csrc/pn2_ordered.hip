@@ -26,9 +26,12 @@
 // ordered_bwd_k: a lane per key j (consecutive lanes, consecutive keys: coalesced stores), CH channels per lane in
 // registers while it walks its row once; the loads of grad_out are scattered inside rows of 4 * N2 bytes that stay in L2.
 // A row's sum is sequential by contract, so a long row is one lane's loop (correct for any length, slow for a
-// degenerate index where one key owns everything).
+// degenerate index where one key owns everything). It is the library's only per-key walk: the feature gradients of the
+// training-mode row builders (pn2_rows.hip: a SetAbstraction's group rows, FeatureAggregation's rows onto the 2D
+// encoder's strided map) are two more entries on it, at the end of this file.
 #include "blockscan.h"
 #include "compact.h"
+#include "pn2_rows.h"
 
 namespace {
 
@@ -144,18 +147,22 @@ __global__ __launch_bounds__(CSR_T) void csr_sort_k(const int64_t* __restrict__ 
   }
 }
 
-// grad_in[b, c, j] = the ordered sum over row (b, j). INTERP: g is (B, C, N2), entry p reads g[b, c, p / 3] * w[b, p];
-// otherwise g is (B, C, L) and entry p reads g[b, c, p]. One workgroup = 256 keys x CH channels of one batch element.
+// out(b, c, j) = the ordered sum over row (b, j), the only per-key walk of the library. The gradient g is a base pointer
+// with a channel stride gc and a batch stride gb: (B, C, G) is (G, C*G), a channel-major operand [C, B*L] is (B*L, L).
+// INTERP: entry p reads g[.., p / 3] * w[b, p]; otherwise entry p reads g[.., p]. The result goes onto a map of nv images
+// of hw keys per batch element with strides s (pn2_rows.h): a plain (B, C, N1) gradient is nv = 1, hw = N1,
+// (C*N1, N1, 1). One workgroup = 256 keys x CH channels of one batch element.
 template <typename T, bool INTERP, int CH>
-__global__ __launch_bounds__(256) void ordered_bwd_k(const T* __restrict__ g, const T* __restrict__ w,
-                                                     const int32_t* __restrict__ row_start,
-                                                     const int32_t* __restrict__ entries, int C, int64_t N1, int64_t L,
-                                                     int64_t G, int64_t total, int nchunk, int nkeyblk,
-                                                     T* __restrict__ gi) {
+__global__ __launch_bounds__(256) void ordered_bwd_k(const T* __restrict__ g, int64_t gc, int64_t gb,
+                                                     const T* __restrict__ w, const int32_t* __restrict__ row_start,
+                                                     const int32_t* __restrict__ entries, int C, int64_t nv, int64_t hw,
+                                                     int64_t L, int64_t total, int nchunk, int nkeyblk,
+                                                     T* __restrict__ out, MapStrides s) {
   const int kb = blockIdx.x % nkeyblk;
   const int bc = blockIdx.x / nkeyblk;
   const int chunk = bc % nchunk;
   const int64_t b = bc / nchunk;
+  const int64_t N1 = nv * hw;
   const int64_t j = (int64_t)kb * 256 + threadIdx.x;
   if (j >= N1) return;
   const int c0 = chunk * CH;
@@ -163,7 +170,7 @@ __global__ __launch_bounds__(256) void ordered_bwd_k(const T* __restrict__ g, co
 #pragma unroll
   for (int u = 0; u < CH; ++u) {
     const int c = c0 + u < C ? c0 + u : C - 1;                           // a chunk's surplus lanes re-read the last channel
-    gp[u] = g + (b * C + c) * G;
+    gp[u] = g + c * gc + b * gb;
   }
   T acc[CH];
 #pragma unroll
@@ -177,37 +184,55 @@ __global__ __launch_bounds__(256) void ordered_bwd_k(const T* __restrict__ g, co
     if (p < 0 || p >= L) continue;
     const int64_t n = INTERP ? p / 3 : p;
     if (INTERP) {
+      // the gathered values first, the weight last: with the weight's load in front the same instructions come out in
+      // a schedule that measured 2 % slower (profiles/rows_refactor_bench.txt)
+      T v[CH];
+#pragma unroll
+      for (int u = 0; u < CH; ++u) v[u] = gp[u][n];
       const T wk = wb[p];
 #pragma unroll
-      for (int u = 0; u < CH; ++u) acc[u] = acc[u] + gp[u][n] * wk;
+      for (int u = 0; u < CH; ++u) acc[u] = acc[u] + v[u] * wk;
     } else {
 #pragma unroll
       for (int u = 0; u < CH; ++u) acc[u] = acc[u] + gp[u][n];
     }
   }
+  T* o = out + map_offset(j, b, nv, hw, s);
 #pragma unroll
   for (int u = 0; u < CH; ++u)
-    if (c0 + u < C) gi[(b * C + c0 + u) * N1 + j] = acc[u];
+    if (c0 + u < C) o[(c0 + u) * s.sc] = acc[u];
 }
 
 inline int64_t csr_scan_blocks(int64_t R) { return cdiv64(R + 1, TPB); }
 
+// what every ordered backward does once its own size refusals have passed: L positions per batch element, the keys of
+// the map (nv, hw, s)
 template <typename T, bool INTERP>
-int ordered_bwd_entry(const char* what, const T* g, const T* w, const int32_t* row_start, const int32_t* entries, int B,
-                      int C, int64_t N1, int64_t N2, int K, T* gi, void* stream) {
+int ordered_bwd_entry(const char* what, const T* g, int64_t gc, int64_t gb, const T* w, const int32_t* row_start,
+                      const int32_t* entries, int B, int C, int64_t nv, int64_t hw, int64_t L, T* out, MapStrides s,
+                      void* stream) {
   constexpr int CH = 8;
-  MVK_REQUIRE(B >= 0 && C >= 0 && N1 >= 0 && N2 >= 0 && K >= 0, "%s: bad sizes", what);
-  const int64_t L = N2 * K;
-  MVK_REQUIRE((int64_t)B * L < CSR_LIMIT && (int64_t)B * N1 < CSR_LIMIT, "%s: B*N2*K and B*N1 must be below 2^31", what);
+  const int64_t N1 = nv * hw;
   if ((int64_t)B * C * N1 == 0) return 0;
-  MVK_REQUIRE(row_start && entries && gi && (L == 0 || (g && (!INTERP || w))), "%s: null operand", what);
+  MVK_REQUIRE(row_start && entries && out && (L == 0 || (g && (!INTERP || w))), "%s: null operand", what);
   const int64_t nchunk = cdiv64(C, CH), nkeyblk = cdiv64(N1, 256);
   const int64_t blocks = (int64_t)B * nchunk * nkeyblk;
   MVK_REQUIRE(blocks < CSR_LIMIT, "%s: too many elements", what);
-  hipLaunchKernelGGL((ordered_bwd_k<T, INTERP, CH>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, w,
-                     row_start, entries, C, N1, L, INTERP ? N2 : L, (int64_t)B * L, (int)nchunk, (int)nkeyblk, gi);
+  hipLaunchKernelGGL((ordered_bwd_k<T, INTERP, CH>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, gc, gb,
+                     w, row_start, entries, C, nv, hw, L, (int64_t)B * L, (int)nchunk, (int)nkeyblk, out, s);
   MVK_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+// feature_interpolate and group_points: grad_out (B, C, N2) or (B, C, N2*K), grad_in (B, C, N1)
+template <typename T, bool INTERP>
+int index_bwd_entry(const char* what, const T* g, const T* w, const int32_t* row_start, const int32_t* entries, int B,
+                    int C, int64_t N1, int64_t N2, int K, T* gi, void* stream) {
+  MVK_REQUIRE(B >= 0 && C >= 0 && N1 >= 0 && N2 >= 0 && K >= 0, "%s: bad sizes", what);
+  const int64_t L = N2 * K, G = INTERP ? N2 : L;
+  MVK_REQUIRE((int64_t)B * L < CSR_LIMIT && (int64_t)B * N1 < CSR_LIMIT, "%s: B*N2*K and B*N1 must be below 2^31", what);
+  return ordered_bwd_entry<T, INTERP>(what, g, G, C * G, w, row_start, entries, B, C, 1, N1, L, gi,
+                                      MapStrides{C * N1, N1, 1}, stream);
 }
 
 }  // namespace
@@ -252,22 +277,42 @@ extern "C" int mvk_index_csr(const int64_t* index, int B, int64_t L, int64_t N1,
 extern "C" int mvk_interpolate_bwd_csr(const float* grad_out, const float* weight, const int32_t* row_start,
                                        const int32_t* entries, int B, int C, int64_t N1, int64_t N2, float* grad_in,
                                        void* stream) {
-  return ordered_bwd_entry<float, true>("interpolate_bwd_csr", grad_out, weight, row_start, entries, B, C, N1, N2, 3,
+  return index_bwd_entry<float, true>("interpolate_bwd_csr", grad_out, weight, row_start, entries, B, C, N1, N2, 3,
                                         grad_in, stream);
 }
 extern "C" int mvk_interpolate_bwd_csr_f64(const double* grad_out, const double* weight, const int32_t* row_start,
                                            const int32_t* entries, int B, int C, int64_t N1, int64_t N2, double* grad_in,
                                            void* stream) {
-  return ordered_bwd_entry<double, true>("interpolate_bwd_csr", grad_out, weight, row_start, entries, B, C, N1, N2, 3,
+  return index_bwd_entry<double, true>("interpolate_bwd_csr", grad_out, weight, row_start, entries, B, C, N1, N2, 3,
                                          grad_in, stream);
 }
 extern "C" int mvk_group_points_bwd_csr(const float* grad_out, const int32_t* row_start, const int32_t* entries, int B,
                                         int C, int64_t N1, int64_t N2, int K, float* grad_in, void* stream) {
-  return ordered_bwd_entry<float, false>("group_points_bwd_csr", grad_out, nullptr, row_start, entries, B, C, N1, N2, K,
+  return index_bwd_entry<float, false>("group_points_bwd_csr", grad_out, nullptr, row_start, entries, B, C, N1, N2, K,
                                          grad_in, stream);
 }
 extern "C" int mvk_group_points_bwd_csr_f64(const double* grad_out, const int32_t* row_start, const int32_t* entries, int B,
                                             int C, int64_t N1, int64_t N2, int K, double* grad_in, void* stream) {
-  return ordered_bwd_entry<double, false>("group_points_bwd_csr", grad_out, nullptr, row_start, entries, B, C, N1, N2, K,
+  return index_bwd_entry<double, false>("group_points_bwd_csr", grad_out, nullptr, row_start, entries, B, C, N1, N2, K,
                                           grad_in, stream);
+}
+
+// The feature gradients of the training-mode row builders (pn2_rows.hip): dX is the channel-major operand [C.., B*L].
+extern "C" int mvk_pn2_sa_rows_bwd_csr(const float* dX, const int32_t* row_start, const int32_t* entries, int B, int C,
+                                       int64_t N, int64_t M, int K, float* dfeature, void* stream) {
+  int64_t R;
+  if (int rc = rows_sizes("pn2_sa_rows_bwd_csr", B, C, N, M, K, &R)) return rc;
+  const int64_t L = M * (int64_t)K;
+  return ordered_bwd_entry<float, false>("pn2_sa_rows_bwd_csr", dX, R, L, nullptr, row_start, entries, B, C, 1, N, L,
+                                         dfeature, MapStrides{C * N, N, 1}, stream);
+}
+extern "C" int mvk_pn2_fa_rows_bwd_csr(const float* dX, const int32_t* row_start, const int32_t* entries, int B, int nv,
+                                       int C, int64_t HW, int64_t N, int K, float* dfeature_2d, int64_t stride_image,
+                                       int64_t stride_channel, int64_t stride_pixel, void* stream) {
+  const MapStrides s{stride_image, stride_channel, stride_pixel};
+  int64_t R, P;
+  if (int rc = fa_sizes("pn2_fa_rows_bwd_csr", B, nv, C, HW, N, K, s, &R, &P)) return rc;
+  const int64_t L = N * (int64_t)K;
+  return ordered_bwd_entry<float, false>("pn2_fa_rows_bwd_csr", dX, R, L, nullptr, row_start, entries, B, C, nv, HW, L,
+                                         dfeature_2d, s, stream);
 }

@@ -2470,7 +2470,7 @@ def pn2_fa_mlp(feature_2d, image_xyz, points, index, params, widths, reduction='
 
 
 # --------------------------------------------------------------------------------------------
-# MVPNet baseline, training mode: group rows and the max over the neighbours (csrc/pn2_train.hip)
+# MVPNet baseline, training mode: group rows and the max over the neighbours (csrc/pn2_rows.hip)
 # --------------------------------------------------------------------------------------------
 
 def _pn2_train_args(name, floats, index=None):
@@ -2488,6 +2488,18 @@ def _pn2_train_args(name, floats, index=None):
         if not index.is_contiguous():
             raise RuntimeError("%s: operands must be contiguous" % name)
     _dev(index, *floats)
+
+
+def _pn2_rows_reduce_args(name, y, B, M, K):
+    """The refusals shared by pn2_rows_max and pn2_rows_sum; returns B, M, K as ints."""
+    _pn2_train_args(name, (y,))
+    B, M, K = int(B), int(M), int(K)
+    if y.dim() != 2 or B < 0 or M < 0 or K < 1 or y.shape[0] != B * M * K:
+        raise RuntimeError("%s: expected y (B*M*K, Cout) with K >= 1, got %s for B=%d M=%d K=%d"
+                           % (name, tuple(y.shape), B, M, K))
+    if y.shape[0] >= 1 << 31:
+        raise RuntimeError("%s: B*M*K = %d rows must be below 2^31" % (name, y.shape[0]))
+    return B, M, K
 
 
 class _PN2SaRowsFn(torch.autograd.Function):
@@ -2575,19 +2587,13 @@ def pn2_rows_max(y, B, M, K, return_arg=False):
     gradient (a ball query pads its rows with copies of the first hit); a NaN propagates as in torch.max. return_arg:
     also that k, int32 (B, Cout, M). One launch forward, one backward (every element of the gradient is written: no zero
     fill, no atomics)."""
-    _pn2_train_args("pn2_rows_max", (y,))
-    B, M, K = int(B), int(M), int(K)
-    if y.dim() != 2 or B < 0 or M < 0 or K < 1 or y.shape[0] != B * M * K:
-        raise RuntimeError("pn2_rows_max: expected y (B*M*K, Cout) with K >= 1, got %s for B=%d M=%d K=%d"
-                           % (tuple(y.shape), B, M, K))
-    if y.shape[0] >= 1 << 31:
-        raise RuntimeError("pn2_rows_max: B*M*K = %d rows must be below 2^31" % y.shape[0])
+    B, M, K = _pn2_rows_reduce_args("pn2_rows_max", y, B, M, K)
     out, arg = _PN2RowsMaxFn.apply(y, B, M, K)
     return (out, arg) if return_arg else out
 
 
 # --------------------------------------------------------------------------------------------
-# MVPNet baseline, training mode: the 2D -> 3D hand-off around FeatureAggregation's shared MLP (csrc/fa_train.hip,
+# MVPNet baseline, training mode: the 2D -> 3D hand-off around FeatureAggregation's shared MLP (csrc/pn2_rows.hip,
 # DESIGN 7o)
 # --------------------------------------------------------------------------------------------
 
@@ -2687,13 +2693,7 @@ def pn2_rows_sum(y, B, M, K):
     """The sum over the neighbours on rows: y (B*M*K, Cout) row-major, row (b*M + m)*K + k (what ops.bn_lrelu returns)
     -> (B, Cout, M): the first row's value, then one rounded float32 addition per further row in ascending k. One launch
     forward, one backward (every element of the gradient is written: no zero fill, no atomics)."""
-    _pn2_train_args("pn2_rows_sum", (y,))
-    B, M, K = int(B), int(M), int(K)
-    if y.dim() != 2 or B < 0 or M < 0 or K < 1 or y.shape[0] != B * M * K:
-        raise RuntimeError("pn2_rows_sum: expected y (B*M*K, Cout) with K >= 1, got %s for B=%d M=%d K=%d"
-                           % (tuple(y.shape), B, M, K))
-    if y.shape[0] >= 1 << 31:
-        raise RuntimeError("pn2_rows_sum: B*M*K = %d rows must be below 2^31" % y.shape[0])
+    B, M, K = _pn2_rows_reduce_args("pn2_rows_sum", y, B, M, K)
     return _PN2RowsSumFn.apply(y, B, M, K)
 
 

@@ -848,7 +848,7 @@ int mvk_group_points_bwd_csr(const float* grad_out, const int32_t* row_start, co
 int mvk_group_points_bwd_csr_f64(const double* grad_out, const int32_t* row_start, const int32_t* entries, int B, int C,
                                  int64_t N1, int64_t N2, int K, double* grad_in, void* stream);
 
-/* ---------------- PointNet++ set abstraction in training mode (csrc/pn2_train.hip) ------------------------- */
+/* ---------------- PointNet++ set abstraction in training mode (csrc/pn2_rows.hip; _bwd_csr: csrc/pn2_ordered.hip) ---- */
 /* The two ends of a SetAbstraction's shared MLP when its products run on mvk_gemm_f32 and its BatchNorm on
  * mvk_bn_lrelu_*: the operand rows of a ball-query group and the maximum over a centroid's K rows, each with its
  * backward. R = B*M*K rows, row r = (b*M + m)*K + k; R must be below 2^31 (refused otherwise). One launch each, no host
@@ -880,7 +880,7 @@ int mvk_pn2_sa_rows_bwd_csr(const float* dX, const int32_t* row_start, const int
 int mvk_pn2_rows_max_fwd(const float* Y, int B, int64_t M, int K, int Cout, float* out, int32_t* arg, void* stream);
 int mvk_pn2_rows_max_bwd(const float* g, const int32_t* arg, int B, int64_t M, int K, int Cout, float* dY, void* stream);
 
-/* ---------------- MVPNet's 2D -> 3D hand-off in training mode (csrc/fa_train.hip) ------------------------- */
+/* ---------------- MVPNet's 2D -> 3D hand-off in training mode (csrc/pn2_rows.hip; _bwd_csr: csrc/pn2_ordered.hip) ---- */
 /* The two ends of FeatureAggregation's shared MLP for a whole batch when its products run on mvk_gemm_f32 and its
  * BatchNorm on mvk_bn_lrelu_*. feature_2d, its three element strides, image_xyz [B, nv * HW, 3], points [B,3,N] and
  * index [B,N,K] (int64 flat pixel indices j = view * HW + pixel in [0, P), P = nv * HW) are those of mvk_pn2_fa_fwd: the

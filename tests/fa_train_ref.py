@@ -1,4 +1,4 @@
-"""NumPy restatement of the training-mode FeatureAggregation kernels (csrc/fa_train.hip), own text.
+"""NumPy restatement of the training-mode FeatureAggregation kernels (csrc/pn2_rows.hip), own text.
 
 The map is (B*nv, C, h, w); a flat pixel index p = view*h*w + pixel of batch element b selects image b*nv + view. Rows:
 R = B*np*k, row r = (b*np + n)*k + j. `fa_rows` builds the channel-major operand X (C [+4], R) in the dtype of its

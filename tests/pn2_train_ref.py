@@ -1,4 +1,4 @@
-"""NumPy restatement of the training-mode set abstraction kernels (csrc/pn2_train.hip), own text.
+"""NumPy restatement of the training-mode set abstraction kernels (csrc/pn2_rows.hip), own text.
 
 Rows: R = B*M*K, row r = (b*M + m)*K + k. `sa_rows` builds the channel-major operand X (Cin, R) of a ball-query group
 in the dtype of its inputs (a gather and ONE rounded subtraction), `rows_max` the maximum over a centroid's K rows with

@@ -1,4 +1,4 @@
-"""CPU-only: the host side of the fused FeatureAggregation training path (csrc/fa_train.hip, ops.pn2_fa_rows /
+"""CPU-only: the host side of the fused FeatureAggregation training path (csrc/pn2_rows.hip, ops.pn2_fa_rows /
 pn2_rows_sum, fuse_training(net, aggregation=True)): exports at ABI 9, the size refusals through the raw library, the
 wrappers' refusals, the plain-attribute switch, and the NumPy restatement of tests/fa_train_ref.py against the unfused
 function written in torch float64 (gather + subtraction + cat + a 1x1 product + sum / max) and its autograd."""

@@ -1,5 +1,5 @@
 """GPU: the fused FeatureAggregation training path. Operator level: ops.pn2_fa_rows / ops.pn2_rows_sum
-(csrc/fa_train.hip) against the NumPy restatement of tests/fa_train_ref.py -- forwards and the ordered backward bit for
+(csrc/pn2_rows.hip) against the NumPy restatement of tests/fa_train_ref.py -- forwards and the ordered backward bit for
 bit, the atomic backward within (T + 1) u sum|g| -- on a map that is NCHW or channels-last. Module and network level:
 FeatureAggregation.forward_rows and MVPNet3D after fuse_training(net, aggregation=True) against the unfused hand-off and
 a float64 run of the same modules under util.referee_check, call counts, fall-backs, bit-reproducibility in deterministic

@@ -1,4 +1,4 @@
-"""CPU-only: the host side of the fused PointNet++ training path (csrc/pn2_train.hip, ops.pn2_sa_rows / pn2_rows_max,
+"""CPU-only: the host side of the fused PointNet++ training path (csrc/pn2_rows.hip, ops.pn2_sa_rows / pn2_rows_max,
 fuse_training): exports at ABI 9, the wrappers' refusals, the plain-attribute switch, and the NumPy restatement of
 tests/pn2_train_ref.py against torch float64 gather + cat + max and its autograd."""
 import ctypes

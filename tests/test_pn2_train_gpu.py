@@ -1,4 +1,4 @@
-"""GPU: the fused PointNet++ training path. Operator level: ops.pn2_sa_rows / ops.pn2_rows_max (csrc/pn2_train.hip)
+"""GPU: the fused PointNet++ training path. Operator level: ops.pn2_sa_rows / ops.pn2_rows_max (csrc/pn2_rows.hip)
 against the NumPy restatement of tests/pn2_train_ref.py -- forwards and the ordered backward bit for bit, the atomic
 backward within (T + 1) u sum|g|. Module and network level: fuse_training against the unfused modules and a float64 run
 of the same modules under util.referee_check, the g16 PointNet++ against its fixture, bit-reproducibility in
@@ -61,13 +61,15 @@ def dyadic(rng, shape):
 
 # ------------------------------------------------------------------------------------------------ group rows
 
-# (B, N, M, K, C, use_xyz, index). Together: B in {1, 3}, N in {9, 70}, M in {1, 7, 65}, K in {1, 5, 32, 33}, rows of
-# 3, 4 (+ 3) and 64 (+ 3) values with and without the coordinates; R from 1 to 6 435 (26 workgroups), every channel-group
-# count of the forward's grid (1, 4, 8). index: "ball" = a real ball query; "made" = ball-like with rows of -1 and pad
-# repeats; "one" = one key owns every position.
+# (B, N, M, K, C, use_xyz, index). Together: B in {1, 2, 3}, N in {1, 9, 70}, M in {1, 3, 7, 65}, K in {1, 2, 5, 32, 33},
+# rows of 3, 4 (+ 3), 8 (+ 3) and 64 (+ 3) values with and without the coordinates; R from 1 to 6 435 (26 workgroups),
+# every channel-group count of the forward's grid (1, 4, 8). index: "ball" = a real ball query; "made" = ball-like with
+# rows of -1 and pad repeats; "one" = one key owns every position. N = 1 with 8 channels: the feature's channel stride is
+# 1, the one shape at which a kernel choice by strides would leave the plane kernels for the channels-last tile.
 ROWS_CASES = [(1, 9, 1, 1, None, True, "ball"), (3, 70, 7, 5, 4, True, "ball"), (1, 70, 65, 32, 64, True, "ball"),
               (3, 9, 65, 33, 4, False, "made"), (1, 70, 7, 33, 64, False, "made"), (3, 70, 1, 32, None, True, "made"),
-              (3, 9, 7, 5, 64, True, "one"), (1, 9, 65, 1, 4, True, "made"), (3, 70, 65, 33, 64, True, "ball")]
+              (3, 9, 7, 5, 64, True, "one"), (1, 9, 65, 1, 4, True, "made"), (3, 70, 65, 33, 64, True, "ball"),
+              (2, 1, 3, 2, 8, True, "made")]
 
 
 def rows_case(ops, b, n, m, k, c, kind, seed):

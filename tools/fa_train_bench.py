@@ -1,5 +1,5 @@
 """Development-only (GPU box): MVPNet3D's 2D -> 3D hand-off in training mode with and without
-fuse_training(net, aggregation=True).
+fuse_training(net, aggregation=True) (row kernels: csrc/pn2_rows.hip).
 
 Workload: the default FeatureAggregation(64, (64, 64, 64)), sum over k, with relation features; nv = 3 views of h x w =
 120 x 160, np = 8 192 points per chunk, k = 3 pixels per point, batches of 1, 8 and 32 chunks; the encoder's map

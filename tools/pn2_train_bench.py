@@ -1,4 +1,5 @@
-"""Development-only (GPU box): a PointNet++ training step with and without fuse_training.
+"""Development-only (GPU box): a PointNet++ training step with and without fuse_training (the row kernels
+are csrc/pn2_rows.hip).
 
 Workload: the default PN2SSG with 64 input channels and 20 classes on 8 192 points per chunk, training mode, batches of
 1, 8 and 32 chunks.
