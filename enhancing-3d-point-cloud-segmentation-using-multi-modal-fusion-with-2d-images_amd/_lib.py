@@ -2,207 +2,145 @@
 
 There is NO fallback: if the HIP library is missing or stale this module raises. PyTorch is used
 only as the owner of device memory and streams -- every signature is plain pointers and sizes.
+
+The header is the only declaration of the ABI. parse_header() reads it when this module is imported -- prototypes,
+struct layouts and integer #defines -- and one mapping from C type to ctypes type turns that into restype / argtypes
+and the Structure classes. The parser knows three forms (function declaration, struct typedef, #define of an integer)
+and raises with the line number on everything else: a header it cannot read completely is an error, never a guess.
+tests/test_abi_binding_cpu.py lets the host compiler check what it read.
 """
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmvkpconv.so")
-ABI_VERSION = 9
+HEADER_PATH = os.path.join(_HERE, "..", "include", "mvkpconv.h")
 
-_vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
-
-
-
-class BnFwdProblem(C.Structure):
-    """mvk_bn_fwd_problem (include/mvkpconv.h): the arguments of mvk_bn_lrelu_fwd for one of two paired problems."""
-    _fields_ = [("x", _vp), ("n_valid", _vp), ("R", _i64), ("D", C.c_int32), ("gamma", _vp), ("beta", _vp), ("eps", _f),
-                ("momentum", _f), ("slope", _f), ("running_mean", _vp), ("running_var", _vp), ("mean", _vp), ("invstd", _vp),
-                ("scratch2D", _vp), ("y", _vp), ("num_batches_tracked", _vp), ("addend", _vp), ("ext_part", _vp),
-                ("ext_rows", C.c_int32)]
-
-
-class BnBwdProblem(C.Structure):
-    """mvk_bn_bwd_problem: the arguments of mvk_bn_lrelu_bwd."""
-    _fields_ = [("x", _vp), ("g", _vp), ("n_valid", _vp), ("R", _i64), ("D", C.c_int32), ("gamma", _vp), ("beta", _vp),
-                ("mean", _vp), ("invstd", _vp), ("slope", _f), ("scratch", _vp), ("dgamma_dbeta", _vp), ("dx", _vp),
-                ("y_out", _vp), ("d_addend", _vp)]
+# canonical C type -> ctypes type. A pointer that is not listed is POINTER(Structure) for a struct of the header and
+# c_void_p otherwise (device and host arrays alike are passed as addresses).
+CTYPES = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double,
+          "const char*": C.c_char_p}
+_SCALARS = frozenset(t for t in CTYPES if not t.endswith("*"))
+_POINTEES = _SCALARS | {"void", "char", "uint8_t", "uint16_t"}      # what a pointer may point to, besides a struct
+_INTEGER = r"-?(?:0[xX][0-9a-fA-F]+|0|[1-9][0-9]*)"
+_DIRECTIVE = re.compile(r"\s*#\s*(?:include\s*<[\w./]+>|ifdef\s+__cplusplus|ifndef\s+\w+_H|endif"      # guard, not a switch
+                        r"|define\s+(\w+)(?:\s+(%s))?)\s*" % _INTEGER)
+_STRUCT = re.compile(r"typedef\s+struct(?:\s+\w+)?\s*\{([^{}]*)\}\s*(mvk_\w+)\s*;")
+_FUNCTION = re.compile(r"([\w\s*]+?)\b(mvk_\w+)\s*\(([^(){};]*)\)\s*;")
 
 
-class RevList(C.Structure):
-    """mvk_rev_list: one reverse list for mvk_reverse_finish_many."""
-    _fields_ = [("rev", _vp), ("counts", _vp), ("status", _vp), ("rows", _i64), ("width", C.c_int32), ("shadow", C.c_int32)]
+def parse_header(text):
+    """(FUNCTIONS, STRUCTS, CONSTANTS) of a header in the style of include/mvkpconv.h:
+    FUNCTIONS {name: (return type, ((type, parameter name), ...))}, STRUCTS {name: ((type, field name), ...)}, both in
+    header order with types in canonical spelling ('const float*', 'int64_t'), CONSTANTS {MVK_NAME: int}."""
+    functions, structs, constants = {}, {}, {}
+
+    def fail(pos, what):
+        pos += len(text[pos:]) - len(text[pos:].lstrip())
+        raise ValueError("mvkpconv.h line %d: %s" % (text.count("\n", 0, pos) + 1, what))
+
+    def canonical(pos, spelling):
+        """[const] <known type word> [*], or it raises."""
+        tokens = re.findall(r"\w+|\S", spelling)
+        const = tokens[:1] == ["const"]
+        base, stars = "".join(tokens[const:const + 1]), tokens[const + 1:]
+        if not (stars == [] and not const and base in _SCALARS
+                or stars == ["*"] and (base in _POINTEES or base in structs)):
+            fail(pos, "unsupported type %r" % " ".join(tokens))
+        return "const " * const + base + "*" * len(stars)
+
+    def declarator(pos, spelling):
+        """'const float* x' -> ('const float*', 'x')"""
+        m = re.fullmatch(r"(.*[\s*])([A-Za-z_]\w*)\s*", spelling, re.S)
+        if not m or m.group(2) == "const" or m.group(2) in _POINTEES:
+            fail(pos, "expected '<type> <name>', found %r" % spelling.strip())
+        return canonical(pos, m.group(1)), m.group(2)
+
+    # a comment becomes a blank and its line breaks, a preprocessor line an empty line: line numbers stay the header's
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", lambda m: " " + "\n" * m.group().count("\n"), text, flags=re.S)
+    lines = text.split("\n")
+    for i, line in enumerate(lines):
+        if line.lstrip().startswith("#"):
+            m = _DIRECTIVE.fullmatch(line)
+            name, value = m.groups() if m else (None, None)
+            if not m or (name is not None and (name.startswith("MVK_") != (value is not None) or name in constants)):
+                raise ValueError("mvkpconv.h line %d: unsupported preprocessor line %r" % (i + 1, line.strip()))
+            if value is not None:
+                constants[name] = int(value, 0)
+            lines[i] = ""
+    text = "\n".join(lines)
+
+    block = re.fullmatch(r'\s*extern\s+"C"\s*\{(.*)\}\s*', text, re.S)
+    if not block:
+        fail(0, 'expected one extern "C" { ... } block around all declarations')
+    pos, end = block.start(1), block.end(1)
+    while True:
+        pos = re.compile(r"\s*").match(text, pos, end).end()
+        if pos == end:
+            return functions, structs, constants
+        s = _STRUCT.match(text, pos, end)
+        f = None if s else _FUNCTION.match(text, pos, end)
+        if (s or f) and (s or f).group(2) in functions.keys() | structs.keys():
+            fail(pos, "%s is declared twice" % (s or f).group(2))
+        if s:
+            fields, at = [], s.start(1)
+            *statements, tail = s.group(1).split(";")
+            if tail.strip() or not statements:
+                fail(s.end(1) - len(tail), "struct %s: expected 'type name;' fields" % s.group(2))
+            for statement in statements:      # 'float eps, momentum, slope' declares three fields
+                first, *more = statement.split(",")
+                ctype, name = declarator(at, first)
+                if more and (ctype.endswith("*") or not all(re.fullmatch(r"\s*[A-Za-z_]\w*\s*", n) for n in more)):
+                    fail(at, "only scalar fields share a declaration, found %r" % statement.strip())
+                fields += [(ctype, n.strip()) for n in [name] + more]
+                at += len(statement) + 1
+            structs[s.group(2)] = tuple(fields)
+        elif f:
+            params, at = [], f.start(3)
+            for spelling in f.group(3).split(",") if f.group(3).strip() != "void" else ():
+                params.append(declarator(at, spelling))
+                at += len(spelling) + 1
+            functions[f.group(2)] = (canonical(pos, f.group(1)), tuple(params))
+        else:
+            fail(pos, "neither a function declaration nor a struct typedef: %r" % text[pos:end].split("\n")[0].strip())
+        pos = (s or f).end()
 
 
-class RegLayer(C.Structure):
-    """mvk_reg_layer: one deformable layer for mvk_deform_regularizer_many."""
-    _fields_ = [("min_d2", _vp), ("deformed_kp", _vp), ("n_valid", _vp), ("d_min_d2", _vp), ("d_deformed_kp", _vp),
-                ("N", _i64), ("extent", _f), ("repulse_extent", _f), ("power", _f)]
+def _bind(functions, structs):
+    """({struct name: Structure class}, {function name: (restype, argtypes)}) through CTYPES."""
+    classes = {}
+
+    def ctype(t):
+        if t in CTYPES:
+            return CTYPES[t]
+        assert t.endswith("*"), t
+        pointee = t[6 * t.startswith("const "):-1]
+        return C.POINTER(classes[pointee]) if pointee in classes else C.c_void_p
+
+    for name, fields in structs.items():
+        classes[name] = type("".join(w.capitalize() for w in name.split("_")[1:]), (C.Structure,),
+                             {"_fields_": [(n, ctype(t)) for t, n in fields], "__doc__": name + " (include/mvkpconv.h)"})
+    return classes, {name: (ctype(ret), [ctype(t) for t, _ in params]) for name, (ret, params) in functions.items()}
 
 
-class BnFinish(C.Structure):
-    """mvk_bn_finish: the producer's half of a folded BatchNorm (statistics finished inside the GEMM launch)."""
-    _fields_ = [("counters", _vp), ("eps", _f), ("momentum", _f), ("mean", _vp), ("invstd", _vp), ("running_mean", _vp),
-                ("running_var", _vp), ("num_batches_tracked", _vp)]
+def _read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError(
+            "include/mvkpconv.h is not there (%s). The binding reads every prototype of libmvkpconv.so from it -- "
+            "run the package from a checkout of the repository; there is no second copy of the C ABI." % HEADER_PATH)
+    with open(HEADER_PATH) as f:
+        return f.read()
 
 
-class ATransform(C.Structure):
-    """mvk_a_transform: the consumer's half (BatchNorm + LeakyReLU applied while the A operand is staged)."""
-    _fields_ = [("mean", _vp), ("invstd", _vp), ("gamma", _vp), ("beta", _vp), ("slope", _f), ("n_valid", _vp), ("out", _vp)]
+FUNCTIONS, STRUCTS, CONSTANTS = parse_header(_read_header())
+_CLASSES, _PROTOTYPES = _bind(FUNCTIONS, STRUCTS)
+EXPORTS = tuple(FUNCTIONS)
+ABI_VERSION = CONSTANTS["MVK_ABI_VERSION"]
+BnFwdProblem, BnBwdProblem = _CLASSES["mvk_bn_fwd_problem"], _CLASSES["mvk_bn_bwd_problem"]
+BnFinish, ATransform = _CLASSES["mvk_bn_finish"], _CLASSES["mvk_a_transform"]
+RevList, RegLayer = _CLASSES["mvk_rev_list"], _CLASSES["mvk_reg_layer"]
 
-
-_SIGNATURES = {
-    "mvk_abi_version": (C.c_int, []),
-    "mvk_last_error": (C.c_char_p, []),
-    "mvk_kpconv_gather_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i, _i, _vp, _i, _vp, _i, _f, _i, _i,
-                                        _vp, _vp, _vp, _vp, _vp]),
-    "mvk_kpconv_gather_fwd_ordered": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i, _i, _vp, _i, _vp, _i, _f, _i, _i,
-                                                _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mvk_gemm_f32_stream_plan": (C.c_int, [_i64, _i, _i64, _vp]),
-    "mvk_gemm_f32_stream": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i, _i64, _vp, _vp, _vp]),
-    "mvk_bn_single_launch_rows": (C.c_int, [_i]),
-    "mvk_kpconv_gather_plan": (C.c_int, [_i64, _i64, _i, _i, _i, _i, _vp]),
-    "mvk_kpconv_scatter_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _vp, _i, _f, _i, _i,
-                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mvk_gemm_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _vp]),
-    "mvk_gemm_f32_plan": (C.c_int, [_i64, _i64, _i64, _i, _i, _vp, _vp]),
-    "mvk_gemm_f32_kp_transposed": (C.c_int, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
-    "mvk_reverse_neighbors": (C.c_int, [_vp, _i, _i64, _i, _i64, _i64, _vp, _i, C.c_int32, _i, _vp, _vp, _vp]),
-    "mvk_gather_sum_rows": (C.c_int, [_vp, _i64, _i64, _vp, _i, _i64, _i, _vp, _vp, _vp]),
-    "mvk_max_pool_bwd_gather": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _vp, _i, _i64, _i, _vp, _vp, _vp]),
-    "mvk_gemm_f32_ldb": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
-    "mvk_gemm_split_arena": (C.c_int, [_vp, _i64, _vp, _i64]),
-    "mvk_gemm_split_ordered": (C.c_int, []),
-    "mvk_gemm_f32_bias_act": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i, _vp, _f, _vp]),
-    "mvk_gemm_f32_scatter_cat": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i, _i64, _i64, _i, _vp, _vp, _vp]),
-    "mvk_gemm_f32_dual_plan": (C.c_int, [_i64, _i64, _i64, _i64, _vp]),
-    "mvk_gemm_f32_dual": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
-    "mvk_gemm_f32_pair_plan": (C.c_int, [_i64, _i64, _i64, _i64, _i, _vp]),
-    "mvk_gemm_f32_pair": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp]),
-    "mvk_gemm_f32_ex": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "mvk_gemm_f32_bn": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, C.POINTER(BnFinish), C.POINTER(ATransform), _vp]),
-    "mvk_gemm_f32_pair_bn": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i, _vp, _vp, _vp,
-                                       C.POINTER(BnFinish), C.POINTER(BnFinish), _vp]),
-    "mvk_gemm_group_entry_bytes": (C.c_int64, []),
-    "mvk_gemm_f32_tn_grouped_split": (C.c_int, [C.c_int64, C.c_int64, C.c_int64]),
-    "mvk_gemm_f32_tn_grouped_plan": (C.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mvk_gemm_f32_tn_grouped": (C.c_int, [_vp, _i, _i, _i64, _i64, _vp]),
-    "mvk_kpconv_gather_rev_deform": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp]),
-    "mvk_kpconv_deform_doff": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i, _i, _vp, _i, _vp, _i, _f, _i, _vp, _vp, _vp, _vp,
-                                        _vp, _vp]),
-    "mvk_deform_regularizer": (C.c_int, [_vp, _vp, _vp, _i64, _i, _f, _f, _f, _vp, _vp, _vp, _vp]),
-    "mvk_deform_regularizer_ex": (C.c_int, [_vp, _vp, _vp, _i64, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
-    "mvk_bias_act_nhwc": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp]),
-    "mvk_sgd_chunk_elems": (C.c_int, []),
-    "mvk_sgd_clip_step": (C.c_int, [_vp, _vp, _i64, _f, _f, _i, _vp]),
-    "mvk_deform_operands_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
-    "mvk_deform_operands_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _f, _vp, _vp, _vp]),
-    "mvk_xent_workspace_floats": (C.c_int64, [_i64]),
-    "mvk_xent_fwd": (C.c_int, [_vp, _i64, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
-    "mvk_xent_bwd": (C.c_int, [_vp, _i64, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
-    "mvk_seg_workspace_floats": (C.c_int64, [_i64]),
-    "mvk_seg_loss_fwd": (C.c_int, [_vp, _i64, _i, _i64, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mvk_seg_loss_fwd_f64": (C.c_int, [_vp, _i64, _i, _i64, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mvk_seg_loss_bwd": (C.c_int, [_vp, _i64, _i, _i64, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mvk_seg_loss_bwd_f64": (C.c_int, [_vp, _i64, _i, _i64, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mvk_bn_lrelu_fwd": (C.c_int, [_vp, _vp, _i64, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                  _vp, _i, _vp]),
-    "mvk_bn_lrelu_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mvk_bn_lrelu_fwd_pair": (C.c_int, [C.POINTER(BnFwdProblem), C.POINTER(BnFwdProblem), _vp]),
-    "mvk_bn_lrelu_bwd_pair": (C.c_int, [C.POINTER(BnBwdProblem), C.POINTER(BnBwdProblem), _vp]),
-    "mvk_bias_lrelu_fwd": (C.c_int, [_vp, _vp, _i64, _i, _f, _vp, _vp]),
-    "mvk_bias_lrelu_bwd": (C.c_int, [_vp, _vp, _i64, _i, _f, _vp, _vp, _vp]),
-    "mvk_add_lrelu_fwd": (C.c_int, [_vp, _vp, _i64, _f, _vp, _vp]),
-    "mvk_add_lrelu_bwd": (C.c_int, [_vp, _vp, _i64, _f, _vp, _vp]),
-    "mvk_max_pool_fwd": (C.c_int, [_vp, _i64, _i, _vp, _i, _i64, _i, _vp, _vp, _vp]),
-    "mvk_max_pool_bwd": (C.c_int, [_vp, _vp, _vp, _i, _i64, _i, _i64, _i, _vp, _vp]),
-    "mvk_gather_rows_fwd": (C.c_int, [_vp, _i64, _i, _vp, _i, _i64, _i64, _vp, _vp]),
-    "mvk_gather_rows_bwd": (C.c_int, [_vp, _vp, _i, _i64, _i64, _i64, _i, _vp, _vp]),
-    "mvk_gather_rows_bwd_ld": (C.c_int, [_vp, _i64, _vp, _i, _i64, _i64, _i64, _i, _vp, _vp]),
-    "mvk_gather_rows_cat_fwd": (C.c_int, [_vp, _i64, _i, _vp, _i, _i64, _i64, _vp, _i, _vp, _vp]),
-    "mvk_gather_rows_cat_bwd": (C.c_int, [_vp, _vp, _i, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp]),
-    "mvk_grid_subsample_workspace": (C.c_int64, [_i64, _i, _i, _i]),
-    "mvk_grid_subsample_batch": (C.c_int, [_vp, _i64, _vp, _i, _vp, _i, _vp, _i, _f, _i, _vp, _vp, _vp, _vp,
-                                           _vp, _vp, _i64, _vp]),
-    "mvk_grid_subsample_batch_oriented": (C.c_int, [_vp, _i64, _vp, _i, _vp, _vp, _i, _vp, _i, _f, _i, _vp, _vp,
-                                                    _vp, _vp, _vp, _vp, _i64, _vp]),
-    "mvk_grid_subsample_batch_dev": (C.c_int, [_vp, _i64, _vp, _i, _vp, _f, _vp, _i64, _f, _vp, _vp, _vp, _vp, _i64,
-                                               _vp]),
-    "mvk_radius_neighbors_dev": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _f, _vp, _i, _i, _vp, _i, _vp, _i64,
-                                           _vp]),
-    "mvk_radius_neighbors_dev_rev": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _f, _vp, _i, _i, _vp, _i, _vp, _i64,
-                                               _vp, _i, _vp, _vp, _vp]),
-    "mvk_reverse_finish_many": (C.c_int, [C.POINTER(RevList), _i, _vp]),
-    "mvk_deform_regularizer_many": (C.c_int, [C.POINTER(RegLayer), _i, _i, _vp, _vp, _vp]),
-    "mvk_neighbors_cell_order": (C.c_int, [_i64, _i, _vp, _vp, _i64, _vp, _i64, _vp]),
-    "mvk_radius_neighbors_workspace": (C.c_int64, [_i64, _i64, _i]),
-    "mvk_radius_neighbors_batch": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _f, _vp, _i, _vp,
-                                             _vp, _i64, _vp]),
-    "mvk_radius_neighbors_enqueue": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _f, _vp, _i, _vp, _i,
-                                               _vp, _i64, _vp]),
-    "mvk_pad_points": (C.c_int, [_vp, _i64, _vp, _i64, _i, _f, _vp, _vp]),
-    "mvk_pad_index_rows": (C.c_int, [_vp, _i, _i64, _i, _i64, _vp, _i64, _i, _i64, _vp]),
-    "mvk_unproject_depth": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "mvk_knn_workspace": (C.c_int64, [_i64, _i64, _i]),
-    "mvk_knn_f64": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i, _vp, _vp, _i64, _vp]),
-    "mvk_ball_query_workspace": (C.c_int64, [_i64]),
-    "mvk_ball_query": (C.c_int, [_vp, _i64, _vp, C.c_double, _vp, _vp, _vp, _vp, _i64, _vp]),
-    "mvk_tukey_update": (C.c_int, [_vp, _i64, _vp, C.c_double, _vp, _vp]),
-    "mvk_fa_gather_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i64, _i64, _i, _vp, _vp]),
-    "mvk_fa_gather_fwd_ex": (C.c_int, [_vp, _i, _vp, _vp, _vp, _i, _i, _i64, _i64, _i, _vp, _vp]),
-    "mvk_group_points_fwd": (C.c_int, [_vp, _vp, _i, _i, _i64, _i64, _i, _vp, _vp]),
-    "mvk_group_points_bwd": (C.c_int, [_vp, _vp, _i, _i, _i64, _i64, _i, _vp, _vp]),
-    "mvk_group_points_fwd_f64": (C.c_int, [_vp, _vp, _i, _i, _i64, _i64, _i, _vp, _vp]),
-    "mvk_group_points_bwd_f64": (C.c_int, [_vp, _vp, _i, _i, _i64, _i64, _i, _vp, _vp]),
-    "mvk_vote_update": (C.c_int, [_vp, _i64, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, C.c_double, C.c_double,
-                                  _f, _vp, _i, _vp, _vp, _i, _vp, _vp]),
-    "mvk_vote_predict": (C.c_int, [_vp, _i64, _i, _vp, _i, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    "mvk_affine_lrelu": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i, _f, _vp, _vp]),
-    "mvk_fps_workspace": (C.c_int64, [_i64, _i64, _i]),
-    "mvk_fps": (C.c_int, [_vp, _i, _i64, _i, _i64, _vp, _vp, _i64, _vp]),
-    "mvk_fps_f64": (C.c_int, [_vp, _i, _i64, _i, _i64, _vp, _vp, _i64, _vp]),
-    "mvk_pn2_ball_query": (C.c_int, [_vp, _vp, _i, _i64, _i64, _f, _i, _vp, _vp, _vp]),
-    "mvk_pn2_ball_query_f64": (C.c_int, [_vp, _vp, _i, _i64, _i64, _f, _i, _vp, _vp, _vp]),
-    "mvk_fps_ragged": (C.c_int, [_vp, _vp, _i, _i64, _i, _i64, _vp, _vp, _i64, _vp]),
-    "mvk_fps_ragged_f64": (C.c_int, [_vp, _vp, _i, _i64, _i, _i64, _vp, _vp, _i64, _vp]),
-    "mvk_pn2_ball_query_ragged": (C.c_int, [_vp, _vp, _vp, _i, _i64, _i64, _f, _i, _vp, _vp, _vp]),
-    "mvk_pn2_ball_query_ragged_f64": (C.c_int, [_vp, _vp, _vp, _i, _i64, _i64, _f, _i, _vp, _vp, _vp]),
-    "mvk_knn_distance": (C.c_int, [_vp, _vp, _i, _i64, _i64, _i, _vp, _vp, _vp]),
-    "mvk_knn_distance_f64": (C.c_int, [_vp, _vp, _i, _i64, _i64, _i, _vp, _vp, _vp]),
-    "mvk_interpolate_fwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _vp]),
-    "mvk_interpolate_fwd_f64": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _vp]),
-    "mvk_interpolate_bwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _vp]),
-    "mvk_interpolate_bwd_f64": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _vp]),
-    "mvk_index_csr_workspace": (C.c_int64, [_i, _i64, _i64]),
-    "mvk_index_csr": (C.c_int, [_vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
-    "mvk_interpolate_bwd_csr": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i64, _i64, _vp, _vp]),
-    "mvk_interpolate_bwd_csr_f64": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i64, _i64, _vp, _vp]),
-    "mvk_group_points_bwd_csr": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _i, _vp, _vp]),
-    "mvk_group_points_bwd_csr_f64": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _i, _vp, _vp]),
-    "mvk_box_count": (C.c_int, [_vp, _i64, _vp, _i, _vp, _vp]),
-    "mvk_box_select_workspace": (C.c_int64, [_i64, _i]),
-    "mvk_box_select": (C.c_int, [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
-    "mvk_chunk_vote_add": (C.c_int, [_vp, _i, _i64, _vp, _i64, _vp, _vp, _i64, _vp]),
-    "mvk_chunk_vote_finish": (C.c_int, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
-    "mvk_chunk_confusion": (C.c_int, [_vp, _vp, _i64, _i, _vp, _vp]),
-    "mvk_pn2_mlp_supported": (C.c_int, [_vp, _i]),
-    "mvk_pn2_sa_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _vp, _vp]),
-    "mvk_pn2_fp_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _vp]),
-    "mvk_pn2_fa_fwd": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _i, _i,
-                                 _vp, _vp]),
-    "mvk_pn2_sa_rows_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _i, _vp, _vp]),
-    "mvk_pn2_sa_rows_bwd": (C.c_int, [_vp, _vp, _i, _i, _i64, _i64, _i, _vp, _vp]),
-    "mvk_pn2_sa_rows_bwd_csr": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _i, _vp, _vp]),
-    "mvk_pn2_rows_max_fwd": (C.c_int, [_vp, _i, _i64, _i, _i, _vp, _vp, _vp]),
-    "mvk_pn2_rows_max_bwd": (C.c_int, [_vp, _vp, _i, _i64, _i, _i, _vp, _vp]),
-    "mvk_pn2_fa_rows_fwd": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _i, _i, _vp, _vp]),
-    "mvk_pn2_fa_rows_bwd": (C.c_int, [_vp, _vp, _i, _i, _i, _i64, _i64, _i, _vp, _i64, _i64, _i64, _vp]),
-    "mvk_pn2_fa_rows_bwd_csr": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i64, _i64, _i, _vp, _i64, _i64, _i64, _vp]),
-    "mvk_pn2_rows_sum_fwd": (C.c_int, [_vp, _i, _i64, _i, _i, _vp, _vp]),
-    "mvk_pn2_rows_sum_bwd": (C.c_int, [_vp, _i, _i64, _i, _i, _vp, _vp]),
-}
-
-EXPORTS = tuple(_SIGNATURES)
 _lib = None
 _owner_pid = None
 
@@ -237,7 +175,7 @@ def lib():
                 "libmvkpconv.so is not built (%s). Run `python __graft_entry__.py build` -- there is "
                 "no CPU fallback for the MV-KPConv hot path." % LIB_PATH)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in _PROTOTYPES.items():
             fn = getattr(l, name)          # AttributeError = missing export = stale build: loud
             fn.restype = res
             fn.argtypes = args

@@ -11,10 +11,11 @@ import weakref
 
 import torch
 
-from ._lib import lib, check
+from ._lib import lib, check, CONSTANTS
 
-INFLUENCE = {"constant": 0, "linear": 1, "gaussian": 2}
-AGGREGATION = {"sum": 0, "closest": 1}
+# the MVK_INFL_* / MVK_AGG_* codes of include/mvkpconv.h under the reference's names (blocks.py:329-354)
+INFLUENCE = {k[len("MVK_INFL_"):].lower(): v for k, v in CONSTANTS.items() if k.startswith("MVK_INFL_")}
+AGGREGATION = {k[len("MVK_AGG_"):].lower(): v for k, v in CONSTANTS.items() if k.startswith("MVK_AGG_")}
 
 
 def _p(t):
@@ -1730,8 +1731,8 @@ def radius_neighbors_dev(queries, supports, q_lens_dev, s_lens_dev, radius, out,
     _NB_GRID.pop(q.device.index, None)
 
 
-REG_MANY = 16           # mvkpconv.h MVK_REG_MANY
-REV_MANY = 12      # include/mvkpconv.h: MVK_REV_MANY
+REG_MANY = CONSTANTS["MVK_REG_MANY"]
+REV_MANY = CONSTANTS["MVK_REV_MANY"]
 
 
 def reverse_finish_many(lists, status=None):
@@ -1787,7 +1788,7 @@ def _rev_counts(n, device):
     return buf
 
 
-REV_MAX_WIDTH = 8192      # include/mvkpconv.h: MVK_REV_MAX_WIDTH
+REV_MAX_WIDTH = CONSTANTS["MVK_REV_MAX_WIDTH"]
 
 
 def reverse_width_cap(sort=None):
