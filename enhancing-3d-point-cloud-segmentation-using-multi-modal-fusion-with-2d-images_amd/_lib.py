@@ -1,4 +1,4 @@
-"""ctypes binding of libmvkpconv.so (C ABI: include/mvkpconv.h).
+"""ctypes binding of libmvkpconv.so (C ABI: include/mvkpconv.h, and include/mvkpconv_scene.h beside it).
 
 There is NO fallback: if the HIP library is missing or stale this module raises. PyTorch is used
 only as the owner of device memory and streams -- every signature is plain pointers and sizes.
@@ -16,6 +16,7 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmvkpconv.so")
 HEADER_PATH = os.path.join(_HERE, "..", "include", "mvkpconv.h")
+SCENE_HEADER_PATH = os.path.join(_HERE, "..", "include", "mvkpconv_scene.h")
 
 # canonical C type -> ctypes type. A pointer that is not listed is POINTER(Structure) for a struct of the header and
 # c_void_p otherwise (device and host arrays alike are passed as addresses).
@@ -124,12 +125,13 @@ def _bind(functions, structs):
     return classes, {name: (ctype(ret), [ctype(t) for t, _ in params]) for name, (ret, params) in functions.items()}
 
 
-def _read_header():
-    if not os.path.exists(HEADER_PATH):
+def _read_header(path=None, name="mvkpconv.h"):
+    path = HEADER_PATH if path is None else path
+    if not os.path.exists(path):
         raise RuntimeError(
-            "include/mvkpconv.h is not there (%s). The binding reads every prototype of libmvkpconv.so from it -- "
-            "run the package from a checkout of the repository; there is no second copy of the C ABI." % HEADER_PATH)
-    with open(HEADER_PATH) as f:
+            "include/%s is not there (%s). The binding reads every prototype of libmvkpconv.so from it -- "
+            "run the package from a checkout of the repository; there is no second copy of the C ABI." % (name, path))
+    with open(path) as f:
         return f.read()
 
 
@@ -137,6 +139,13 @@ FUNCTIONS, STRUCTS, CONSTANTS = parse_header(_read_header())
 _CLASSES, _PROTOTYPES = _bind(FUNCTIONS, STRUCTS)
 EXPORTS = tuple(FUNCTIONS)
 ABI_VERSION = CONSTANTS["MVK_ABI_VERSION"]
+
+# the second header (whole-scene inputs, csrc/scene_inputs.hip): same parser, same library, its own tables -- the
+# declaration of ABI 9 above is not extended by it. It declares functions and constants only.
+SCENE_FUNCTIONS, _scene_structs, SCENE_CONSTANTS = parse_header(_read_header(SCENE_HEADER_PATH, "mvkpconv_scene.h"))
+if _scene_structs or SCENE_FUNCTIONS.keys() & FUNCTIONS.keys() or SCENE_CONSTANTS.keys() & CONSTANTS.keys():
+    raise ValueError("mvkpconv_scene.h: it may declare neither a struct nor a name of mvkpconv.h")
+_SCENE_PROTOTYPES = _bind(SCENE_FUNCTIONS, {})[1]
 BnFwdProblem, BnBwdProblem = _CLASSES["mvk_bn_fwd_problem"], _CLASSES["mvk_bn_bwd_problem"]
 BnFinish, ATransform = _CLASSES["mvk_bn_finish"], _CLASSES["mvk_a_transform"]
 RevList, RegLayer = _CLASSES["mvk_rev_list"], _CLASSES["mvk_reg_layer"]
@@ -175,7 +184,7 @@ def lib():
                 "libmvkpconv.so is not built (%s). Run `python __graft_entry__.py build` -- there is "
                 "no CPU fallback for the MV-KPConv hot path." % LIB_PATH)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _PROTOTYPES.items():
+        for name, (res, args) in list(_PROTOTYPES.items()) + list(_SCENE_PROTOTYPES.items()):
             fn = getattr(l, name)          # AttributeError = missing export = stale build: loud
             fn.restype = res
             fn.argtypes = args

@@ -7,16 +7,13 @@
 // written order, like the NumPy / scikit-learn code they replace.
 #include "common.h"
 #include "compact.h"
+#include "unproject.h"
 
 namespace {
 
 // ---------------------------------------------------------------------------------------------
-// xyz_cam = (Kinv . [u, v, 1]) * depth ;  valid = z_cam > 0 ;  xyz_world = xyz_cam . R^T + t
+// xyz_cam = (Kinv . [u, v, 1]) * depth ;  valid = z_cam > 0 ;  xyz_world = xyz_cam . R^T + t  (unproject.h)
 // ---------------------------------------------------------------------------------------------
-struct Cam {
-  double kinv[9];
-};
-
 __global__ void unproject_kernel(const uint16_t* __restrict__ depth, int nv, int h, int w, Cam cam,
                                  const float* __restrict__ poses, double* __restrict__ xyz,
                                  uint8_t* __restrict__ valid) {
@@ -26,17 +23,11 @@ __global__ void unproject_kernel(const uint16_t* __restrict__ depth, int nv, int
   const int view = (int)(t / hw);
   const int pix = (int)(t % hw);
   const double u = (double)(pix % w), v = (double)(pix / w);
-  // depth: uint16 mm -> float32 / 1000.f (ScanNet_sphere_color.py:410), then promoted to float64
-  const double d = (double)((float)depth[t] / 1000.f);
-  double c[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) c[r] = ((cam.kinv[r * 3] * u + cam.kinv[r * 3 + 1] * v) + cam.kinv[r * 3 + 2]) * d;
+  double c[3], x[3];
+  unproject_pixel(cam, poses + view * 16, u, v, depth[t], c, x);
   valid[t] = c[2] > 0.0;
-  const float* P = poses + view * 16;
 #pragma unroll
-  for (int r = 0; r < 3; ++r)
-    xyz[t * 3 + r] = ((c[0] * (double)P[r * 4] + c[1] * (double)P[r * 4 + 1]) + c[2] * (double)P[r * 4 + 2]) +
-                     (double)P[r * 4 + 3];
+  for (int r = 0; r < 3; ++r) xyz[t * 3 + r] = x[r];
 }
 
 // ---------------------------------------------------------------------------------------------

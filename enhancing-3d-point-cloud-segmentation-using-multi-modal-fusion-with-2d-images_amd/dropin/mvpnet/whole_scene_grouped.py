@@ -8,6 +8,7 @@ and neighbours it gets alone.
 * ``collate_chunks``               several chunks' tensors as one padded batch with 'lengths'
 * ``chunk_groups``                 the chunks of an iterable G at a time, sparse chunks padded the reference's way
 * ``predict_whole_scene_grouped``  the loop; with chunks_per_forward = 1 it is ``predict_whole_scene`` itself
+* ``vote_groups``                  the model / vote loop over such groups, shared with mvpnet/whole_scene_inputs.py
 
 ``test_mvpnet_3d.py`` carries a test file's name and stays as it is, so the loop is a function of its own here and not
 a keyword of ``predict_whole_scene``; the padding of a sparse chunk and the scaffold around the loop are restated
@@ -97,6 +98,17 @@ def predict_whole_scene_grouped(model, points, chunk_inputs, min_nb_pts=2048, se
     if chunks_per_forward == 1:
         return predict_whole_scene(model, points, chunk_inputs, min_nb_pts=min_nb_pts, seg_label=seg_label,
                                    evaluator=evaluator, num_classes=num_classes)
+    return vote_groups(model, points, chunk_groups(chunk_inputs, chunks_per_forward, min_nb_pts, points.device),
+                       seg_label=seg_label, evaluator=evaluator, num_classes=num_classes,
+                       who="predict_whole_scene_grouped")
+
+
+def vote_groups(model, points, groups, seg_label=None, evaluator=None, num_classes=None, who="vote_groups"):
+    """The model / vote loop of ``predict_whole_scene_grouped`` over an iterable of (data_batch, [chunk_ind, ...]) as
+    ``chunk_groups`` yields them: under model.eval() and torch.no_grad() every batch is forwarded once and its chunks
+    vote one by one in order, then the scene is finished (and scored, with seg_label and an evaluator). An exception
+    that the iterable raises leaves the model in its mode and the evaluator untouched. Returns (pred_label, mean_logit)
+    in HBM."""
     device = points.device
     num_points = len(points)
     if num_classes is None and evaluator is not None:
@@ -106,7 +118,7 @@ def predict_whole_scene_grouped(model, points, chunk_inputs, min_nb_pts=2048, se
     model.eval()
     try:
         with torch.no_grad():
-            for data_batch, chunk_inds in chunk_groups(chunk_inputs, chunks_per_forward, min_nb_pts, device):
+            for data_batch, chunk_inds in groups:
                 seg_logit = model(data_batch)['seg_logit']                      # (G, num_classes, n_max)
                 if voter is None:
                     voter = WholeSceneVoter(num_points, seg_logit.shape[1] if num_classes is None else num_classes, device)
@@ -116,6 +128,6 @@ def predict_whole_scene_grouped(model, points, chunk_inputs, min_nb_pts=2048, se
         model.train(was_training)
     if voter is None:
         if num_classes is None:
-            raise ValueError("predict_whole_scene_grouped: a scene without chunks needs num_classes or an evaluator")
+            raise ValueError("%s: a scene without chunks needs num_classes or an evaluator" % who)
         voter = WholeSceneVoter(num_points, num_classes, device)
     return voter.finish(seg_label, evaluator)

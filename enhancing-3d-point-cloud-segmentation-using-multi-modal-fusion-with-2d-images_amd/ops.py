@@ -3333,3 +3333,133 @@ def chunk_confusion(pred, labels, num_classes, confusion=None):
     confusion = _confusion_arg(confusion, int(num_classes), pred.device, "chunk_confusion")
     check(lib().mvk_chunk_confusion(_p(pred), _p(labels), pred.shape[0], int(num_classes), _p(confusion), _stream()))
     return confusion
+
+
+# --------------------------------------------------------------------------------------------
+# MVPNet whole-scene test: the inputs of G chunks at a time (csrc/scene_inputs.hip, include/mvkpconv_scene.h)
+# --------------------------------------------------------------------------------------------
+
+def _i64_vec(t, n, what):
+    if t.dtype != torch.int64 or t.dim() != 1 or t.shape[0] != n:
+        raise RuntimeError("%s: an int64 vector of %d entries expected" % (what, n))
+    return t.contiguous()
+
+
+def overlap_pack(overlap):
+    """pointwise_rgbd_overlap (nb, nf) bool / uint8 in HBM -> frame-major bit rows [nf, ceil(nb / 32)] int32: bit b % 32 of
+    word b // 32 of row f is set when base point b is seen by frame f; bits past nb are zero. Once per scene."""
+    _dev(overlap)
+    if overlap.dim() != 2 or overlap.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError("overlap_pack: a bool or uint8 (nb, nf) table expected")
+    ov = overlap.contiguous()
+    nb, nf = ov.shape
+    packed = torch.empty((nf, (nb + 31) // 32), device=ov.device, dtype=torch.int32)
+    check(lib().mvk_overlap_pack(_p(ov), nb, nf, _p(packed), _stream()))
+    return packed
+
+
+def chunk_select_frames(packed, nb, base_point_ind, rows, row_off, row_len, num_frames):
+    """sel [G, num_frames] int32 (HBM): the greedy maximum-coverage frame choice of utils.voting.select_frames for G
+    chunks in one launch. packed: ``overlap_pack`` of the scan's table of nb base points; base_point_ind [nb] int64; chunk
+    g is rows[row_off[g] : row_off[g] + row_len[g]] (all int64, HBM), ASCENDING and DISTINCT as scene2chunks_legacy makes
+    it. Ties go to the lower frame; frame 0 is chosen once nothing is left to cover. Nothing is read back."""
+    _dev(packed, base_point_ind, rows, row_off, row_len)
+    nb = int(nb)
+    if packed.dtype != torch.int32 or packed.dim() != 2 or packed.shape[1] != (nb + 31) // 32 or not packed.is_contiguous():
+        raise RuntimeError("chunk_select_frames: packed must be overlap_pack's contiguous int32 [nf, ceil(nb / 32)] rows")
+    bpi = _i64_vec(base_point_ind, nb, "chunk_select_frames: base_point_ind")
+    G = row_off.shape[0]
+    rows = _i64_vec(rows, rows.shape[0], "chunk_select_frames: rows")
+    row_off, row_len = _i64_vec(row_off, G, "chunk_select_frames: row_off"), _i64_vec(row_len, G, "chunk_select_frames: row_len")
+    sel = torch.empty((G, int(num_frames)), device=packed.device, dtype=torch.int32)
+    check(lib().mvk_chunk_select_frames(_p(packed), nb, packed.shape[0], _p(bpi), _p(rows), rows.shape[0], _p(row_off),
+                                        _p(row_len), G, int(num_frames), _p(sel), _stream()))
+    return sel
+
+
+def chunk_unproject(sel, depth16, images, poses, cam_inv, bounds):
+    """The chosen frames sel [G, nv] int32 of G chunks, unprojected as ``unproject_depth`` does it, masked and gathered in
+    one launch: (keys [G, nv*h*w, 3] f64, image_xyz [G,nv,h,w,3] f32, image_mask [G,nv,h,w] bool, images [G,nv,3,h,w] f32,
+    num_valid [G] int32). depth16 (nf,h,w) int16 (the bits of uint16 millimetres), images (nf,h,w,3) f32, poses (nf,4,4)
+    f32 in HBM; cam_inv: the HOST float64 [3,3] inverse intrinsics; bounds [G,4] f64 in HBM (xlo, xhi, ylo, yhi): a pixel
+    is valid when z_cam > 0 and it lies strictly inside them, in float64."""
+    _dev(sel, depth16, images, poses, bounds)
+    if sel.dtype != torch.int32 or sel.dim() != 2 or not sel.is_contiguous():
+        raise RuntimeError("chunk_unproject: sel must be a contiguous int32 [G, nv] tensor")
+    G, nv = sel.shape
+    if depth16.dtype != torch.int16 or depth16.dim() != 3 or not depth16.is_contiguous():
+        raise RuntimeError("chunk_unproject: depth must be a contiguous int16 (nf, h, w) tensor")
+    nf, h, w = depth16.shape
+    if images.dtype != torch.float32 or tuple(images.shape) != (nf, h, w, 3) or not images.is_contiguous():
+        raise RuntimeError("chunk_unproject: images must be a contiguous float32 (nf, h, w, 3) tensor")
+    if poses.dtype != torch.float32 or tuple(poses.shape) != (nf, 4, 4) or not poses.is_contiguous():
+        raise RuntimeError("chunk_unproject: poses must be a contiguous float32 (nf, 4, 4) tensor")
+    if bounds.dtype != torch.float64 or tuple(bounds.shape) != (G, 4) or not bounds.is_contiguous():
+        raise RuntimeError("chunk_unproject: bounds must be a contiguous float64 [G, 4] tensor")
+    kinv = _np.ascontiguousarray(cam_inv, dtype=_np.float64)
+    if kinv.shape != (3, 3):
+        raise RuntimeError("chunk_unproject: cam_inv must be a host [3, 3] array")
+    dev = sel.device
+    keys = torch.empty((G, nv * h * w, 3), device=dev, dtype=torch.float64)
+    image_xyz = torch.empty((G, nv, h, w, 3), device=dev, dtype=torch.float32)
+    image_mask = torch.empty((G, nv, h, w), device=dev, dtype=torch.bool)
+    out = torch.empty((G, nv, 3, h, w), device=dev, dtype=torch.float32)
+    num_valid = torch.empty((G,), device=dev, dtype=torch.int32)
+    check(lib().mvk_chunk_unproject(_p(sel), G, nv, _p(depth16), _p(images), _p(poses), nf, h, w,
+                                    kinv.ctypes.data_as(C.c_void_p), _p(bounds), _p(keys), _p(image_xyz), _p(image_mask),
+                                    _p(out), _p(num_valid), _stream()))
+    return keys, image_xyz, image_mask, out, num_valid
+
+
+def chunk_knn_many(points, rows, row_off, q_off, row_len_host, keys, key_valid, k=3):
+    """(queries [sum, 3] f32, knn [sum, k] int64): the points of G chunks (rows[row_off[g] : row_off[g] + row_len_host[g]]
+    of points [N,3] f32) gathered behind each other at q_off (the running sum of the lengths, [G+1] int64 in HBM), and
+    their exact float64 k-NN among chunk g's keys [G, nk, 3] f64 where key_valid [G, nk] (bool / uint8): ``knn_pixels``
+    once per chunk from one C call. row_len_host: the G lengths on the HOST. -1 where a chunk has fewer than k valid keys."""
+    _dev(points, rows, row_off, q_off, keys, key_valid)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError("chunk_knn_many: points [N,3] float32 expected")
+    pts = points.contiguous()
+    lens = _np.ascontiguousarray(row_len_host, dtype=_np.int64).reshape(-1)
+    G = lens.shape[0]
+    qh = _np.zeros(G + 1, _np.int64)
+    _np.cumsum(lens, out=qh[1:])
+    rows = _i64_vec(rows, rows.shape[0], "chunk_knn_many: rows")
+    row_off, q_off = _i64_vec(row_off, G, "chunk_knn_many: row_off"), _i64_vec(q_off, G + 1, "chunk_knn_many: q_off")
+    if keys.dtype != torch.float64 or keys.dim() != 3 or keys.shape[0] != G or keys.shape[2] != 3 or not keys.is_contiguous():
+        raise RuntimeError("chunk_knn_many: keys must be a contiguous float64 [G, nk, 3] tensor")
+    nk = keys.shape[1]
+    if key_valid.dtype not in (torch.bool, torch.uint8) or key_valid.numel() != G * nk or not key_valid.is_contiguous():
+        raise RuntimeError("chunk_knn_many: key_valid must be a contiguous bool or uint8 tensor of G * nk entries")
+    total = int(qh[-1])
+    queries = torch.empty((total, 3), device=pts.device, dtype=torch.float32)
+    knn = torch.empty((total, int(k)), device=pts.device, dtype=torch.int64)
+    lp, qp = lens.ctypes.data_as(C.c_void_p), qh.ctypes.data_as(C.c_void_p)
+    ws = _workspace("knn", lib().mvk_scene_inputs_workspace(lp, G, nk, int(k)), pts.device)
+    check(lib().mvk_chunk_knn_many(_p(pts), pts.shape[0], _p(rows), rows.shape[0], _p(row_off), _p(q_off), lp, qp, G, _p(keys),
+                                   _p(key_valid), nk, int(k), _p(queries), _p(knn), _p(ws), ws.numel(), _stream()))
+    return queries, knn
+
+
+def chunk_batch_rows(queries, knn, q_off, row_len, lengths, extras, extra_off, n_max):
+    """(points [G, 3, n_max] f32, knn_indices [G, n_max, k] int64): the group as ``collate_chunks`` stacks it. Column j of
+    chunk g is its row j for j < row_len[g], its row extras[extra_off[g] + j - row_len[g]] for j < lengths[g] (the pad of
+    a sparse chunk; extras int32, may be empty) and zero behind. queries / knn / q_off as ``chunk_knn_many`` returns and
+    takes them; row_len, lengths [G] and extra_off [G+1] int64, all in HBM."""
+    _dev(queries, knn, q_off, row_len, lengths, extras, extra_off)
+    G = row_len.shape[0]
+    if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != 3 or not queries.is_contiguous():
+        raise RuntimeError("chunk_batch_rows: queries must be a contiguous float32 [sum, 3] tensor")
+    if knn.dtype != torch.int64 or knn.dim() != 2 or knn.shape[0] != queries.shape[0] or not knn.is_contiguous():
+        raise RuntimeError("chunk_batch_rows: knn must be a contiguous int64 [sum, k] tensor")
+    if extras.dtype != torch.int32 or extras.dim() != 1 or not extras.is_contiguous():
+        raise RuntimeError("chunk_batch_rows: extras must be a contiguous int32 vector")
+    q_off, extra_off = _i64_vec(q_off, G + 1, "chunk_batch_rows: q_off"), _i64_vec(extra_off, G + 1, "chunk_batch_rows: extra_off")
+    row_len, lengths = _i64_vec(row_len, G, "chunk_batch_rows: row_len"), _i64_vec(lengths, G, "chunk_batch_rows: lengths")
+    k, n_max = knn.shape[1], int(n_max)
+    points_out = torch.empty((G, 3, n_max), device=queries.device, dtype=torch.float32)
+    knn_out = torch.empty((G, n_max, k), device=queries.device, dtype=torch.int64)
+    check(lib().mvk_chunk_batch_rows(_p(queries), _p(knn), _p(q_off), _p(row_len), _p(lengths),
+                                     _p(extras) if extras.numel() else None, _p(extra_off), G, n_max, k, _p(points_out),
+                                     _p(knn_out), _stream()))
+    return points_out, knn_out
