@@ -1,4 +1,5 @@
-"""ctypes binding of libmvkpconv.so (C ABI: include/mvkpconv.h, and include/mvkpconv_scene.h beside it).
+"""ctypes binding of libmvkpconv.so (C ABI: include/mvkpconv.h, with include/mvkpconv_scene.h and
+include/mvkpconv_train.h beside it).
 
 There is NO fallback: if the HIP library is missing or stale this module raises. PyTorch is used
 only as the owner of device memory and streams -- every signature is plain pointers and sizes.
@@ -17,6 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmvkpconv.so")
 HEADER_PATH = os.path.join(_HERE, "..", "include", "mvkpconv.h")
 SCENE_HEADER_PATH = os.path.join(_HERE, "..", "include", "mvkpconv_scene.h")
+TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "mvkpconv_train.h")
 
 # canonical C type -> ctypes type. A pointer that is not listed is POINTER(Structure) for a struct of the header and
 # c_void_p otherwise (device and host arrays alike are passed as addresses).
@@ -146,6 +148,13 @@ SCENE_FUNCTIONS, _scene_structs, SCENE_CONSTANTS = parse_header(_read_header(SCE
 if _scene_structs or SCENE_FUNCTIONS.keys() & FUNCTIONS.keys() or SCENE_CONSTANTS.keys() & CONSTANTS.keys():
     raise ValueError("mvkpconv_scene.h: it may declare neither a struct nor a name of mvkpconv.h")
 _SCENE_PROTOTYPES = _bind(SCENE_FUNCTIONS, {})[1]
+
+# the third header (training batches from resident scenes, csrc/train_inputs.hip): the same again
+TRAIN_FUNCTIONS, _train_structs, TRAIN_CONSTANTS = parse_header(_read_header(TRAIN_HEADER_PATH, "mvkpconv_train.h"))
+if (_train_structs or TRAIN_FUNCTIONS.keys() & (FUNCTIONS.keys() | SCENE_FUNCTIONS.keys())
+        or TRAIN_CONSTANTS.keys() & (CONSTANTS.keys() | SCENE_CONSTANTS.keys())):
+    raise ValueError("mvkpconv_train.h: it may declare neither a struct nor a name of the other two headers")
+_TRAIN_PROTOTYPES = _bind(TRAIN_FUNCTIONS, {})[1]
 BnFwdProblem, BnBwdProblem = _CLASSES["mvk_bn_fwd_problem"], _CLASSES["mvk_bn_bwd_problem"]
 BnFinish, ATransform = _CLASSES["mvk_bn_finish"], _CLASSES["mvk_a_transform"]
 RevList, RegLayer = _CLASSES["mvk_rev_list"], _CLASSES["mvk_reg_layer"]
@@ -184,7 +193,7 @@ def lib():
                 "libmvkpconv.so is not built (%s). Run `python __graft_entry__.py build` -- there is "
                 "no CPU fallback for the MV-KPConv hot path." % LIB_PATH)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_PROTOTYPES.items()) + list(_SCENE_PROTOTYPES.items()):
+        for name, (res, args) in list(_PROTOTYPES.items()) + list(_SCENE_PROTOTYPES.items()) + list(_TRAIN_PROTOTYPES.items()):
             fn = getattr(l, name)          # AttributeError = missing export = stale build: loud
             fn.restype = res
             fn.argtypes = args

@@ -14,14 +14,13 @@
 // Integer arithmetic, or float64 in the written order (-ffp-contract=off). The only atomics are integer counters summed
 // in LDS first. A workgroup never straddles two chunks, so per-chunk values are read at wave-uniform addresses.
 #include "common.h"
+#include "select_frames.h"
 #include "unproject.h"
 #include "../../include/mvkpconv_scene.h"
 
 namespace {
 
 constexpr int OP_T = 256;        // threads of the pack kernel
-constexpr int SF_T = 512;        // threads of the selection kernel: 8 waves share out the frames
-constexpr int SF_WAVES = SF_T / 64;
 constexpr int UP_T = 256;        // threads of the unprojection kernel
 constexpr int BR_T = 256;        // threads of the gather kernels
 constexpr int64_t MAX_GRID = ((int64_t)1 << 31) - 1;
@@ -40,25 +39,7 @@ __global__ __launch_bounds__(OP_T) void overlap_pack_k(const uint8_t* __restrict
   packed[f * W + w] = bits;
 }
 
-// is v among row[0 .. n) (ascending, distinct)?
-__device__ __forceinline__ bool row_holds(const int64_t* __restrict__ row, int64_t n, int64_t v) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (row[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  return lo < n && row[lo] == v;
-}
-
-// the better of two (count, frame) pairs: the larger count, the lower frame among equals
-__device__ __forceinline__ void take_better(int& c, int& f, int oc, int of) {
-  if (oc > c || (oc == c && of < f)) {
-    c = oc;
-    f = of;
-  }
-}
-
-// LDS: alive [W] words | count [nf] int32 (dynamic), the pick (static)
+// LDS: alive [W] words | count [nf] int32 (dynamic), the pick (static). The choice itself is select_frames.h's.
 __global__ __launch_bounds__(SF_T) void select_frames_k(const uint32_t* __restrict__ packed, int nb, int nf, int W,
                                                         const int64_t* __restrict__ base_point_ind,
                                                         const int64_t* __restrict__ rows, int64_t total,
@@ -67,56 +48,12 @@ __global__ __launch_bounds__(SF_T) void select_frames_k(const uint32_t* __restri
                                                         int32_t* __restrict__ sel) {
   extern __shared__ uint32_t s_mem[];
   __shared__ int s_pick;
-  uint32_t* s_alive = s_mem;
-  int* s_count = (int*)(s_mem + W);
-  const int g = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = blockIdx.x;
   int64_t j0 = row_off[g], n = row_len[g];
   if (j0 < 0 || j0 > total || n < 0) n = 0;               // a row that leaves the CSR is cut to it
   else if (n > total - j0) n = total - j0;
-  const int64_t* row = rows + (n > 0 ? j0 : 0);
-
-  // step 1: 64 base points per ballot are two words of the mask
-  for (int b0 = wave * 64; b0 < nb; b0 += SF_T) {
-    const int b = b0 + lane;
-    const bool in = b < nb && n > 0 && row_holds(row, n, base_point_ind[b]);
-    const unsigned long long m = __ballot(in);
-    if (lane == 0) {
-      const int w = b0 >> 5;
-      s_alive[w] = (uint32_t)m;
-      if (w + 1 < W) s_alive[w + 1] = (uint32_t)(m >> 32);
-    }
-  }
-  __syncthreads();
-
-  // step 2
-  for (int r = 0; r < nv; ++r) {
-    for (int f = wave; f < nf; f += SF_WAVES) {
-      const uint32_t* __restrict__ bits = packed + (int64_t)f * W;
-      int c = 0;
-      for (int w = lane; w < W; w += 64) c += __popc(bits[w] & s_alive[w]);
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-      if (lane == 0) s_count[f] = c;
-    }
-    __syncthreads();
-    if (wave == 0) {
-      int bc = -1, bf = nf;
-      for (int f = lane; f < nf; f += 64) take_better(bc, bf, s_count[f], f);
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const int oc = __shfl_xor(bc, o), of = __shfl_xor(bf, o);
-        take_better(bc, bf, oc, of);
-      }
-      if (lane == 0) {
-        s_pick = bf;
-        sel[(int64_t)g * nv + r] = bf;
-      }
-    }
-    __syncthreads();
-    const uint32_t* __restrict__ bits = packed + (int64_t)s_pick * W;
-    for (int w = threadIdx.x; w < W; w += SF_T) s_alive[w] &= ~bits[w];
-    __syncthreads();
-  }
+  select_frames_wg(packed, nb, nf, W, base_point_ind, 0, rows + (n > 0 ? j0 : 0), n, nv, sel + (int64_t)g * nv, s_mem,
+                   (int*)(s_mem + W), &s_pick);
 }
 
 __global__ __launch_bounds__(UP_T) void chunk_unproject_k(const int32_t* __restrict__ sel, int nv,

@@ -11,7 +11,7 @@ import weakref
 
 import torch
 
-from ._lib import lib, check, CONSTANTS
+from ._lib import lib, check, CONSTANTS, SCENE_CONSTANTS, TRAIN_CONSTANTS
 
 # the MVK_INFL_* / MVK_AGG_* codes of include/mvkpconv.h under the reference's names (blocks.py:329-354)
 INFLUENCE = {k[len("MVK_INFL_"):].lower(): v for k, v in CONSTANTS.items() if k.startswith("MVK_INFL_")}
@@ -3463,3 +3463,196 @@ def chunk_batch_rows(queries, knn, q_off, row_len, lengths, extras, extra_off, n
                                      _p(extras) if extras.numel() else None, _p(extra_off), G, n_max, k, _p(points_out),
                                      _p(knn_out), _stream()))
     return points_out, knn_out
+
+
+# --------------------------------------------------------------------------------------------
+# MVPNet training batches from scenes resident in HBM (csrc/train_inputs.hip, include/mvkpconv_train.h)
+# --------------------------------------------------------------------------------------------
+
+class TrainResident(object):
+    """S scenes one after another in HBM and their table, as include/mvkpconv_train.h lays them out: points [P,3] f32,
+    labels [P] int64, base_point_ind [NB] int64, bits [NW] int32 (each scene's ``overlap_pack`` rows), depth16 [F,h,w]
+    int16, images [F,h,w,3] f32, poses [F,4,4] f32, cam_inv [S,9] f64, all contiguous in HBM, and table: a HOST int64
+    [S,8] array (point_off, num_points, base_off, num_base, frame_off, num_frames, bits_off in words, 0). The table is
+    checked here -- every scene inside the buffers, behind its predecessor, with a point and a frame, num_base /
+    num_frames within MVK_SCENE_MAX_BASE / MVK_SCENE_MAX_FRAMES -- and uploaded once."""
+
+    def __init__(self, points, labels, base_point_ind, bits, depth16, images, poses, cam_inv, table):
+        _dev(points, labels, base_point_ind, bits, depth16, images, poses, cam_inv)
+        table = _np.ascontiguousarray(table, dtype=_np.int64)
+        if table.ndim != 2 or table.shape[1] != 8:
+            raise RuntimeError("TrainResident: table must be a host int64 [S, 8] array")
+        S = table.shape[0]
+        F = depth16.shape[0] if depth16.dim() == 3 else -1
+        for name, t, dtype, shape in (("points", points, torch.float32, (points.shape[0], 3)),
+                                      ("labels", labels, torch.int64, (points.shape[0],)),
+                                      ("base_point_ind", base_point_ind, torch.int64, (base_point_ind.shape[0],)),
+                                      ("bits", bits, torch.int32, (bits.shape[0],)),
+                                      ("depth16", depth16, torch.int16, tuple(depth16.shape[:3])),
+                                      ("images", images, torch.float32, tuple(depth16.shape[:3]) + (3,)),
+                                      ("poses", poses, torch.float32, (F, 4, 4)),
+                                      ("cam_inv", cam_inv, torch.float64, (S, 9))):
+            if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                raise RuntimeError("TrainResident: %s must be a contiguous %s tensor of shape %s (got %s %s)"
+                                   % (name, str(dtype).replace("torch.", ""), shape, t.dtype, tuple(t.shape)))
+        self.points, self.labels, self.base_point_ind, self.bits = points, labels, base_point_ind, bits
+        self.depth16, self.images, self.poses, self.cam_inv = depth16, images, poses, cam_inv
+        self.S, self.P, self.NB, self.NW, self.F = S, points.shape[0], base_point_ind.shape[0], bits.shape[0], F
+        self.h, self.w = depth16.shape[1], depth16.shape[2]
+        at = [0, 0, 0, 0]
+        for s, (po, n, bo, nb, fo, nf, wo, _) in enumerate(table.tolist()):
+            words = nf * ((nb + 31) // 32)
+            if n < 1 or nf < 1:
+                raise RuntimeError("TrainResident: scene %d has no point or no frame" % s)
+            if nb < 0 or nb > SCENE_CONSTANTS["MVK_SCENE_MAX_BASE"] or nf > SCENE_CONSTANTS["MVK_SCENE_MAX_FRAMES"]:
+                raise RuntimeError("TrainResident: scene %d has %d base points (<= %d) and %d frames (<= %d); there is no "
+                                   "fallback" % (s, nb, SCENE_CONSTANTS["MVK_SCENE_MAX_BASE"], nf,
+                                                 SCENE_CONSTANTS["MVK_SCENE_MAX_FRAMES"]))
+            if po < at[0] or bo < at[1] or fo < at[2] or wo < at[3] or po + n > self.P or bo + nb > self.NB or \
+                    fo + nf > self.F or wo + words > self.NW:
+                raise RuntimeError("TrainResident: scene %d overlaps its predecessor or leaves the buffers" % s)
+            at = [po + n, bo + nb, fo + nf, wo + words]
+        self.table_host = table
+        self.max_points = int(table[:, 1].max()) if S else 0
+        self.max_base = int(table[:, 3].max()) if S else 0
+        self.max_frames = int(table[:, 5].max()) if S else 0
+        staged = torch.empty((S, 8), dtype=torch.int64, pin_memory=True)
+        staged.numpy()[:] = table
+        self.table = staged.to(points.device, non_blocking=True)
+
+    def _totals(self):
+        return self.P, self.NB, self.F, self.NW
+
+
+def _train_items(who, res, scene_id):
+    if not isinstance(res, TrainResident):
+        raise RuntimeError("%s: a TrainResident expected" % who)
+    _dev(scene_id)
+    return _i64_vec(scene_id, scene_id.shape[0], who + ": scene_id"), scene_id.shape[0]
+
+
+def _pair32(v, what):
+    a = _np.asarray(v, dtype=_np.float32).reshape(-1)
+    if a.shape[0] != 2:
+        raise RuntimeError("%s: an (x, y) pair expected" % what)
+    return float(a[0]), float(a[1])
+
+
+def train_chunk_pick(res, scene_id, centers, row_off, total, chunk_size=(1.5, 1.5), chunk_margin=(0.2, 0.2),
+                     chunk_thresh=0.3, max_points=None):
+    """The random crop of ScanNet2D3DChunks.__getitem__ (scannet_2d3d.py:340-371) for B items in four launches:
+    (counts [B,T,2] int32, chosen [B] int32, box [B,4] f32, rows [total] int64, row_len [B] int64), all in HBM.
+    scene_id [B] int64; centers [B,T] int64, the scene-local point numbers of the T tries, drawn by the caller; row_off
+    [B] int64 in HBM, the running sum of the items' num_points, and total, its end, on the host. chosen is the first try
+    with a point of which at least chunk_thresh are labeled, -1 for the whole scene; box = (lo.x, lo.y, hi.x, hi.y) with
+    the margin; the chunk's row holds the GLOBAL indices of its points, ascending. Nothing is read back."""
+    sid, B = _train_items("train_chunk_pick", res, scene_id)
+    _dev(centers, row_off)
+    if centers.dtype != torch.int64 or centers.dim() != 2 or centers.shape[0] != B or not centers.is_contiguous():
+        raise RuntimeError("train_chunk_pick: centers must be a contiguous int64 [B, T] tensor")
+    T = centers.shape[1]
+    row_off = _i64_vec(row_off, B, "train_chunk_pick: row_off")
+    (sx, sy), (mx, my) = _pair32(chunk_size, "train_chunk_pick: chunk_size"), _pair32(chunk_margin, "train_chunk_pick: chunk_margin")
+    max_points = res.max_points if max_points is None else int(max_points)
+    dev, total = sid.device, int(total)
+    tile = TRAIN_CONSTANTS["MVK_TRAIN_PICK_TILE"]
+    block_counts = torch.empty((B * max(1, -(-max_points // tile)),), device=dev, dtype=torch.int32)
+    counts = torch.empty((B, T, 2), device=dev, dtype=torch.int32)
+    chosen = torch.empty((B,), device=dev, dtype=torch.int32)
+    box = torch.empty((B, 4), device=dev, dtype=torch.float32)
+    rows = torch.empty((total,), device=dev, dtype=torch.int64)
+    row_len = torch.empty((B,), device=dev, dtype=torch.int64)
+    check(lib().mvk_train_chunk_pick(_p(res.points), _p(res.labels), res.P, _p(res.table), res.S, res.NB, res.F, res.NW,
+                                     _p(sid), _p(centers), B, T, sx, sy, mx, my, float(chunk_thresh), max_points,
+                                     _p(row_off), total, _p(block_counts), _p(counts), _p(chosen), _p(box), _p(rows),
+                                     _p(row_len), _stream()))
+    return counts, chosen, box, rows, row_len
+
+
+def train_chunk_resample(rows, row_off, row_len, seeds, nb_pts, key_bits=32):
+    """(sample_rows [B,nb_pts] int64, sample_pos [B,nb_pts] int32): nb_pts entries of every row
+    rows[row_off[b] : row_off[b] + row_len[b]] by the library's rule (include/mvkpconv_train.h: a hash of seeds[b] and the
+    position; a row of at least nb_pts entries gives a uniformly drawn subset in ASCENDING position, a shorter one itself
+    and hashed pads). sample_pos are positions in the row, sample_rows the row's entries there; -1 of an empty row.
+    key_bits < 32 shortens the key so that ties occur (for tests)."""
+    _dev(rows, row_off, row_len, seeds)
+    B = seeds.shape[0]
+    rows = _i64_vec(rows, rows.shape[0], "train_chunk_resample: rows")
+    row_off, row_len = _i64_vec(row_off, B, "train_chunk_resample: row_off"), _i64_vec(row_len, B, "train_chunk_resample: row_len")
+    seeds = _i64_vec(seeds, B, "train_chunk_resample: seeds")
+    nb_pts = int(nb_pts)
+    sample_rows = torch.empty((B, nb_pts), device=rows.device, dtype=torch.int64)
+    sample_pos = torch.empty((B, nb_pts), device=rows.device, dtype=torch.int32)
+    check(lib().mvk_train_chunk_resample(_p(rows), rows.shape[0], _p(row_off), _p(row_len), _p(seeds), B, nb_pts,
+                                         int(key_bits), _p(sample_rows), _p(sample_pos), _stream()))
+    return sample_rows, sample_pos
+
+
+def train_select_frames(res, scene_id, rows, row_off, row_len, num_frames):
+    """sel [B, num_frames] int32, scene-local: ``chunk_select_frames`` with item b reading the bit rows and base points of
+    scene scene_id[b]. rows / row_off / row_len as ``train_chunk_pick`` returns and takes them (global indices)."""
+    sid, B = _train_items("train_select_frames", res, scene_id)
+    _dev(rows, row_off, row_len)
+    rows = _i64_vec(rows, rows.shape[0], "train_select_frames: rows")
+    row_off, row_len = _i64_vec(row_off, B, "train_select_frames: row_off"), _i64_vec(row_len, B, "train_select_frames: row_len")
+    sel = torch.empty((B, int(num_frames)), device=sid.device, dtype=torch.int32)
+    check(lib().mvk_train_select_frames(_p(res.bits), res.NW, _p(res.base_point_ind), res.NB, _p(res.table), res.S, res.P,
+                                        res.F, _p(sid), _p(rows), rows.shape[0], _p(row_off), _p(row_len), B,
+                                        int(num_frames), res.max_base, res.max_frames, _p(sel), _stream()))
+    return sel
+
+
+def _rot_arg(who, rot, B):
+    if rot is None:
+        return None
+    _dev(rot)
+    if rot.dtype != torch.float64 or rot.numel() != B * 9 or not rot.is_contiguous():
+        raise RuntimeError("%s: rot must be a contiguous float64 [B, 9] tensor" % who)
+    return rot
+
+
+def train_unproject(res, sel, scene_id, box, flips=None, rot=None):
+    """``chunk_unproject`` for items of different scenes: (keys [B, nv*h*w, 3] f64, image_xyz [B,nv,h,w,3] f32, image_mask
+    [B,nv,h,w] bool, images [B,nv,3,h,w] f32, num_valid [B] int32). sel [B,nv] int32 scene-local frames; box [B,4] f32
+    of ``train_chunk_pick`` (widened by 0.1 in float64, strict); flips [B,nv] uint8 / bool: the view mirrored left to
+    right in every output; rot [B,9] f64: image_xyz rotated after its rounding to float32, keys not."""
+    sid, B = _train_items("train_unproject", res, scene_id)
+    _dev(sel, box, flips)
+    if sel.dtype != torch.int32 or sel.dim() != 2 or sel.shape[0] != B or not sel.is_contiguous():
+        raise RuntimeError("train_unproject: sel must be a contiguous int32 [B, nv] tensor")
+    nv, h, w = sel.shape[1], res.h, res.w
+    if box.dtype != torch.float32 or tuple(box.shape) != (B, 4) or not box.is_contiguous():
+        raise RuntimeError("train_unproject: box must be a contiguous float32 [B, 4] tensor")
+    if flips is not None and (flips.dtype not in (torch.uint8, torch.bool) or flips.numel() != B * nv or not flips.is_contiguous()):
+        raise RuntimeError("train_unproject: flips must be a contiguous uint8 or bool [B, nv] tensor")
+    rot = _rot_arg("train_unproject", rot, B)
+    dev = sid.device
+    keys = torch.empty((B, nv * h * w, 3), device=dev, dtype=torch.float64)
+    image_xyz = torch.empty((B, nv, h, w, 3), device=dev, dtype=torch.float32)
+    image_mask = torch.empty((B, nv, h, w), device=dev, dtype=torch.bool)
+    out = torch.empty((B, nv, 3, h, w), device=dev, dtype=torch.float32)
+    num_valid = torch.empty((B,), device=dev, dtype=torch.int32)
+    check(lib().mvk_train_unproject(_p(sel), _p(sid), B, nv, _p(res.table), res.S, res.P, res.NB, res.F, res.NW,
+                                    _p(res.depth16), _p(res.images), _p(res.poses), _p(res.cam_inv), h, w, _p(box),
+                                    _p(flips), _p(rot), _p(keys), _p(image_xyz), _p(image_mask), _p(out), _p(num_valid),
+                                    _stream()))
+    return keys, image_xyz, image_mask, out, num_valid
+
+
+def train_batch_rows(queries, labels, sample_rows, rot=None):
+    """(points [B, 3, nb_pts] f32, seg_label [B, nb_pts] int64): queries [B*nb_pts, 3] f32 (``chunk_knn_many``'s gather of
+    the sampled points) rotated by rot [B,9] f64 in float64 and rounded to float32 (None: copied), and labels [P] int64
+    at sample_rows [B, nb_pts] int64 (-100 where a row is -1)."""
+    _dev(queries, labels, sample_rows)
+    if sample_rows.dtype != torch.int64 or sample_rows.dim() != 2 or not sample_rows.is_contiguous():
+        raise RuntimeError("train_batch_rows: sample_rows must be a contiguous int64 [B, nb_pts] tensor")
+    B, nb_pts = sample_rows.shape
+    if queries.dtype != torch.float32 or tuple(queries.shape) != (B * nb_pts, 3) or not queries.is_contiguous():
+        raise RuntimeError("train_batch_rows: queries must be a contiguous float32 [B * nb_pts, 3] tensor")
+    labels = _i64_vec(labels, labels.shape[0], "train_batch_rows: labels")
+    rot = _rot_arg("train_batch_rows", rot, B)
+    points_out = torch.empty((B, 3, nb_pts), device=queries.device, dtype=torch.float32)
+    seg_label = torch.empty((B, nb_pts), device=queries.device, dtype=torch.int64)
+    check(lib().mvk_train_batch_rows(_p(queries), _p(labels), labels.shape[0], _p(sample_rows), _p(rot), B, nb_pts,
+                                     _p(points_out), _p(seg_label), _stream()))
+    return points_out, seg_label
