@@ -1,5 +1,5 @@
-"""ctypes binding of libmvkpconv.so (C ABI: include/mvkpconv.h, with include/mvkpconv_scene.h and
-include/mvkpconv_train.h beside it).
+"""ctypes binding of libmvkpconv.so (C ABI: include/mvkpconv.h, with include/mvkpconv_scene.h,
+include/mvkpconv_train.h and include/mvkpconv_sphere.h beside it).
 
 There is NO fallback: if the HIP library is missing or stale this module raises. PyTorch is used
 only as the owner of device memory and streams -- every signature is plain pointers and sizes.
@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(_HERE, "libmvkpconv.so")
 HEADER_PATH = os.path.join(_HERE, "..", "include", "mvkpconv.h")
 SCENE_HEADER_PATH = os.path.join(_HERE, "..", "include", "mvkpconv_scene.h")
 TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "mvkpconv_train.h")
+SPHERE_HEADER_PATH = os.path.join(_HERE, "..", "include", "mvkpconv_sphere.h")
 
 # canonical C type -> ctypes type. A pointer that is not listed is POINTER(Structure) for a struct of the header and
 # c_void_p otherwise (device and host arrays alike are passed as addresses).
@@ -155,6 +156,14 @@ if (_train_structs or TRAIN_FUNCTIONS.keys() & (FUNCTIONS.keys() | SCENE_FUNCTIO
         or TRAIN_CONSTANTS.keys() & (CONSTANTS.keys() | SCENE_CONSTANTS.keys())):
     raise ValueError("mvkpconv_train.h: it may declare neither a struct nor a name of the other two headers")
 _TRAIN_PROTOTYPES = _bind(TRAIN_FUNCTIONS, {})[1]
+
+# the fourth header (sphere batches of the KPFCNN networks, csrc/sphere_inputs.hip): the same again
+SPHERE_FUNCTIONS, _sphere_structs, SPHERE_CONSTANTS = parse_header(_read_header(SPHERE_HEADER_PATH, "mvkpconv_sphere.h"))
+if (_sphere_structs
+        or SPHERE_FUNCTIONS.keys() & (FUNCTIONS.keys() | SCENE_FUNCTIONS.keys() | TRAIN_FUNCTIONS.keys())
+        or SPHERE_CONSTANTS.keys() & (CONSTANTS.keys() | SCENE_CONSTANTS.keys() | TRAIN_CONSTANTS.keys())):
+    raise ValueError("mvkpconv_sphere.h: it may declare neither a struct nor a name of the other three headers")
+_SPHERE_PROTOTYPES = _bind(SPHERE_FUNCTIONS, {})[1]
 BnFwdProblem, BnBwdProblem = _CLASSES["mvk_bn_fwd_problem"], _CLASSES["mvk_bn_bwd_problem"]
 BnFinish, ATransform = _CLASSES["mvk_bn_finish"], _CLASSES["mvk_a_transform"]
 RevList, RegLayer = _CLASSES["mvk_rev_list"], _CLASSES["mvk_reg_layer"]
@@ -193,7 +202,8 @@ def lib():
                 "libmvkpconv.so is not built (%s). Run `python __graft_entry__.py build` -- there is "
                 "no CPU fallback for the MV-KPConv hot path." % LIB_PATH)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_PROTOTYPES.items()) + list(_SCENE_PROTOTYPES.items()) + list(_TRAIN_PROTOTYPES.items()):
+        for name, (res, args) in list(_PROTOTYPES.items()) + list(_SCENE_PROTOTYPES.items()) + list(_TRAIN_PROTOTYPES.items()) \
+                + list(_SPHERE_PROTOTYPES.items()):
             fn = getattr(l, name)          # AttributeError = missing export = stale build: loud
             fn.restype = res
             fn.argtypes = args

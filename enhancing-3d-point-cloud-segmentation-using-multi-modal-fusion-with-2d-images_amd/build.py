@@ -1,4 +1,5 @@
-"""Builds libmvkpconv.so (the C-ABI HIP library, include/mvkpconv.h, include/mvkpconv_scene.h and include/mvkpconv_train.h) in-tree for gfx950.
+"""Builds libmvkpconv.so (the C-ABI HIP library, include/mvkpconv.h, include/mvkpconv_scene.h, include/mvkpconv_train.h and
+include/mvkpconv_sphere.h) in-tree for gfx950.
 
 hipcc cross-compiles without a GPU; the built .so is git-ignored but travels to the GPU box.
 Usage:  python <pkg>/build.py [--force]
@@ -37,6 +38,7 @@ SOURCES = [
     ("pn2_rows.hip", ["-ffp-contract=off"]),      # group / aggregation rows: differences and squared distance as torch rounds them
     ("scene_inputs.hip", ["-ffp-contract=off"]),  # float64 unprojection and box mask: fusion.hip's expression (unproject.h)
     ("train_inputs.hip", ["-ffp-contract=off"]),  # float32 crop boxes as NumPy rounds them, the same unprojection, float64 rotation
+    ("sphere_inputs.hip", ["-ffp-contract=off"]),  # the ragged k-NN: fusion.hip's float64 distances (knn_core.h)
 ]
 
 
@@ -58,6 +60,7 @@ def build_library(force=False, verbose=False):
     hipcc = _hipcc()
     common = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "blockscan.h"), os.path.join(CSRC, "compact.h"),
               os.path.join(CSRC, "pn2_rows.h"), os.path.join(CSRC, "unproject.h"), os.path.join(CSRC, "select_frames.h"),
+              os.path.join(CSRC, "knn_core.h"), os.path.join(HERE, "..", "include", "mvkpconv_sphere.h"),
               os.path.join(HERE, "..", "include", "mvkpconv.h"), os.path.join(HERE, "..", "include", "mvkpconv_scene.h"),
               os.path.join(HERE, "..", "include", "mvkpconv_train.h"),
               os.path.join(HERE, "..", "include", "mvk_prime_list.h"), os.path.abspath(__file__)]

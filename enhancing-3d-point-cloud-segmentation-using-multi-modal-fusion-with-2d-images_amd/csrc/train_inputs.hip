@@ -20,6 +20,7 @@
 // in LDS first. A workgroup never straddles two items, so per-item values are read at wave-uniform addresses.
 #include "common.h"
 #include "compact.h"
+#include "resident.h"
 #include "select_frames.h"
 #include "unproject.h"
 #include "../../include/mvkpconv_scene.h"
@@ -35,31 +36,8 @@ constexpr int UP_T = 256;                          // threads of the unprojectio
 constexpr int BR_T = 256;                          // threads of the row kernel
 constexpr int MAX_T = MVK_TRAIN_MAX_TRIES;
 constexpr int64_t MAX_GRID = ((int64_t)1 << 31) - 1;
-constexpr int64_t MAX_SIZE = (int64_t)1 << 31;
 constexpr int64_t IGNORE_LABEL = -100;
 static_assert(PK_T == COMPACT_T, "the pick kernels scan their tile counts with compact.h");
-
-struct Totals {
-  int64_t P, NB, F, NW;
-};
-
-struct Scene {
-  int64_t point_off, num_points, base_off, num_base, frame_off, num_frames, bits_off;
-  bool ok;
-};
-
-// Row `id` of the table, checked against the totals: a row that leaves them is an empty scene.
-__device__ __forceinline__ Scene load_scene(const int64_t* __restrict__ scenes, int S, const Totals& t, int64_t id) {
-  Scene s = {0, 0, 0, 0, 0, 0, 0, false};
-  if (id < 0 || id >= S) return s;
-  const int64_t* __restrict__ r = scenes + id * 8;
-  const int64_t po = r[0], np = r[1], bo = r[2], nb = r[3], fo = r[4], nf = r[5], wo = r[6];
-  if (po < 0 || np < 0 || po > t.P || np > t.P - po || bo < 0 || nb < 0 || bo > t.NB || nb > t.NB - bo || fo < 0 ||
-      nf < 0 || fo > t.F || nf > t.F - fo || wo < 0 || wo > t.NW || nf * ((nb + 31) >> 5) > t.NW - wo)
-    return s;
-  s = {po, np, bo, nb, fo, nf, wo, true};
-  return s;
-}
 
 struct Crop {
   float sx, sy, mx, my;
@@ -430,10 +408,6 @@ __global__ __launch_bounds__(BR_T) void train_batch_rows_k(const float* __restri
   for (int r = 0; r < 3; ++r) points_out[((int64_t)b * 3 + r) * nb_pts + j] = o[r];
   const int64_t i = sample_rows[q];
   seg_label[q] = i >= 0 && i < P ? labels[i] : IGNORE_LABEL;
-}
-
-bool totals_ok(int64_t P, int64_t NB, int64_t F, int64_t NW, int S) {
-  return P >= 0 && NB >= 0 && F >= 0 && NW >= 0 && S >= 0 && P < MAX_SIZE && NB < MAX_SIZE && F < MAX_SIZE && NW < MAX_SIZE;
 }
 
 }  // namespace

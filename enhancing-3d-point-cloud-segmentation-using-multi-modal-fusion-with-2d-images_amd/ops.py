@@ -11,7 +11,7 @@ import weakref
 
 import torch
 
-from ._lib import lib, check, CONSTANTS, SCENE_CONSTANTS, TRAIN_CONSTANTS
+from ._lib import lib, check, CONSTANTS, SCENE_CONSTANTS, TRAIN_CONSTANTS, SPHERE_CONSTANTS
 
 # the MVK_INFL_* / MVK_AGG_* codes of include/mvkpconv.h under the reference's names (blocks.py:329-354)
 INFLUENCE = {k[len("MVK_INFL_"):].lower(): v for k, v in CONSTANTS.items() if k.startswith("MVK_INFL_")}
@@ -3656,3 +3656,212 @@ def train_batch_rows(queries, labels, sample_rows, rot=None):
     check(lib().mvk_train_batch_rows(_p(queries), _p(labels), labels.shape[0], _p(sample_rows), _p(rot), B, nb_pts,
                                      _p(points_out), _p(seg_label), _stream()))
     return points_out, seg_label
+
+
+# --------------------------------------------------------------------------------------------
+# KPFCNN sphere batches from scenes resident in HBM (csrc/sphere_inputs.hip, include/mvkpconv_sphere.h)
+# --------------------------------------------------------------------------------------------
+
+def knn_f64_ragged(points, rows, q_off, keys, key_valid=None, k=3, return_queries=False):
+    """The exact float64 k-NN of B items whose lengths exist only on the device, in a fixed number of launches: ``knn_pixels``
+    on every item alone, bit for bit. points [N,3] f32; rows [cap] int64; q_off [B+1] int64 in HBM, non-decreasing: the
+    query at slot s of [q_off[b], q_off[b+1]) is points[rows[s]] (zero when rows[s] lies outside [0, N)) and searches
+    keys[b] ([B,nk,3] f64) where key_valid[b] ([B,nk] bool / uint8, None: all). Returns knn [cap,k] int64, the key's number
+    in its item, -1 where the item has no valid key left and in the slots at or past q_off[B]; with return_queries also
+    the gathered queries [cap,3] f32 (zeros past q_off[B]). Nothing is read back."""
+    _dev(points, rows, q_off, keys, key_valid)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
+        raise RuntimeError("knn_f64_ragged: points must be a contiguous float32 [N, 3] tensor")
+    if keys.dtype != torch.float64 or keys.dim() != 3 or keys.shape[2] != 3 or not keys.is_contiguous():
+        raise RuntimeError("knn_f64_ragged: keys must be a contiguous float64 [B, nk, 3] tensor")
+    B, nk, k = keys.shape[0], keys.shape[1], int(k)
+    cap = rows.shape[0]
+    rows, q_off = _i64_vec(rows, cap, "knn_f64_ragged: rows"), _i64_vec(q_off, B + 1, "knn_f64_ragged: q_off")
+    if key_valid is not None and (key_valid.dtype not in (torch.bool, torch.uint8) or key_valid.numel() != B * nk
+                                  or not key_valid.is_contiguous()):
+        raise RuntimeError("knn_f64_ragged: key_valid must be a contiguous bool or uint8 tensor of B * nk entries")
+    if not 1 <= k <= 8:
+        raise RuntimeError("knn_f64_ragged: k=%d unsupported (1..8)" % k)
+    nbytes = lib().mvk_knn_ragged_workspace(B, cap, nk, k) if B else 0
+    if nbytes < 0:
+        raise RuntimeError("knn_f64_ragged: B=%d items (1..%d) or cap + B * nk = %d (< 2^30) refused"
+                           % (B, SPHERE_CONSTANTS["MVK_KNN_RAGGED_MAX_ITEMS"], cap + B * nk))
+    dev = points.device
+    knn = torch.empty((cap, k), device=dev, dtype=torch.int64)
+    queries = torch.empty((cap, 3), device=dev, dtype=torch.float32) if return_queries else None
+    if B == 0:
+        knn.fill_(-1)
+        if queries is not None:
+            queries.zero_()
+    else:
+        ws = _workspace("knn_ragged", nbytes, dev)
+        check(lib().mvk_knn_f64_ragged(_p(points), points.shape[0], _p(rows), cap, _p(q_off), B, _p(keys), _p(key_valid), nk,
+                                       k, _p(knn), _p(queries), _p(ws), ws.numel(), _stream()))
+    return (knn, queries) if return_queries else knn
+
+
+class SphereResident(object):
+    """What the sphere batches need beside a ``TrainResident`` (whose points are the dl-subsampled clouds): colors [P,3]
+    f32, the coarse potential points pot_points [PP,3] f32 of all scenes back to back, potentials [PP] f64, all contiguous
+    in HBM, and pots: a HOST int64 [S,2] array (pot_off, num_pot). The table is checked here -- every scene's potential
+    points inside the buffer, behind its predecessor, at least one -- and uploaded once; min_potentials [S] f64 and
+    argmin_potentials [S] int64 (scene-local, the first among equals) are computed from the potentials."""
+
+    def __init__(self, res, colors, pot_points, potentials, pots):
+        if not isinstance(res, TrainResident):
+            raise RuntimeError("SphereResident: a TrainResident expected")
+        _dev(colors, pot_points, potentials)
+        pots = _np.ascontiguousarray(pots, dtype=_np.int64)
+        if pots.ndim != 2 or tuple(pots.shape) != (res.S, 2):
+            raise RuntimeError("SphereResident: pots must be a host int64 [S, 2] array")
+        PP = pot_points.shape[0]
+        for name, t, dtype, shape in (("colors", colors, torch.float32, (res.P, 3)),
+                                      ("pot_points", pot_points, torch.float32, (PP, 3)),
+                                      ("potentials", potentials, torch.float64, (PP,))):
+            if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                raise RuntimeError("SphereResident: %s must be a contiguous %s tensor of shape %s (got %s %s)"
+                                   % (name, str(dtype).replace("torch.", ""), shape, t.dtype, tuple(t.shape)))
+        at = 0
+        for s, (off, n) in enumerate(pots.tolist()):
+            if n < 1:
+                raise RuntimeError("SphereResident: scene %d has no potential point" % s)
+            if off < at or off + n > PP:
+                raise RuntimeError("SphereResident: the potential points of scene %d overlap its predecessor's or leave "
+                                   "the buffer" % s)
+            at = off + n
+        self.res, self.colors, self.pot_points, self.potentials = res, colors, pot_points, potentials
+        self.PP, self.pots_host = PP, pots
+        staged = torch.empty((res.S, 2), dtype=torch.int64, pin_memory=True)
+        staged.numpy()[:] = pots
+        self.pots = staged.to(colors.device, non_blocking=True)
+        mins = [torch.min(potentials[off:off + n], 0) for off, n in pots.tolist()]
+        self.min_potentials = torch.stack([m.values for m in mins]) if mins else potentials.new_zeros((0,))
+        self.argmin_potentials = (torch.stack([m.indices for m in mins]) if mins
+                                  else torch.zeros((0,), dtype=torch.int64, device=colors.device))
+
+
+def _sphere_res(who, sres):
+    if not isinstance(sres, SphereResident):
+        raise RuntimeError("%s: a SphereResident expected" % who)
+    return sres.res
+
+
+def _slots(who, B_max):
+    B_max = int(B_max)
+    if not 0 <= B_max <= SPHERE_CONSTANTS["MVK_SPHERE_MAX_SLOTS"]:
+        raise RuntimeError("%s: %d sphere slots (0..%d)" % (who, B_max, SPHERE_CONSTANTS["MVK_SPHERE_MAX_SLOTS"]))
+    return B_max
+
+
+def sphere_pick(sres, in_radius, batch_limit, max_spheres):
+    """potential_item's picks (ScanNet_sphere_color.py:556-602, :690-694) for up to max_spheres spheres in one launch:
+    (cloud_ind [B_max] int64, point_ind [B_max] int64, centers [B_max,3] f32, lengths [B_max] int32, num_spheres [1]
+    int32), all in HBM; the resident potentials and their minima are updated. The loop ends behind the sphere with which
+    the sum of the lengths exceeds batch_limit; slots never reached hold -1 / zeros. Nothing is read back."""
+    res = _sphere_res("sphere_pick", sres)
+    B_max = _slots("sphere_pick", max_spheres)
+    dev = sres.colors.device
+    cloud_ind = torch.empty((B_max,), device=dev, dtype=torch.int64)
+    point_ind = torch.empty((B_max,), device=dev, dtype=torch.int64)
+    centers = torch.empty((B_max, 3), device=dev, dtype=torch.float32)
+    lengths = torch.empty((B_max,), device=dev, dtype=torch.int32)
+    num_spheres = torch.zeros((1,), device=dev, dtype=torch.int32)
+    check(lib().mvk_sphere_pick(_p(sres.pot_points), sres.PP, _p(sres.potentials), _p(sres.pots), _p(sres.min_potentials),
+                                _p(sres.argmin_potentials), _p(res.points), res.P, _p(res.table), res.S, res.NB, res.F,
+                                res.NW, float(in_radius), int(batch_limit), B_max, _p(cloud_ind), _p(point_ind),
+                                _p(centers), _p(lengths), _p(num_spheres), _stream()))
+    return cloud_ind, point_ind, centers, lengths, num_spheres
+
+
+def _slot_args(who, cloud_ind, centers):
+    _dev(cloud_ind, centers)
+    B_max = _slots(who, cloud_ind.shape[0])
+    cloud_ind = _i64_vec(cloud_ind, B_max, who + ": cloud_ind")
+    if centers.dtype != torch.float32 or tuple(centers.shape) != (B_max, 3) or not centers.is_contiguous():
+        raise RuntimeError("%s: centers must be a contiguous float32 [B_max, 3] tensor" % who)
+    return cloud_ind, B_max
+
+
+def sphere_members(res, cloud_ind, centers, radius, cap, status=None):
+    """(rows [cap] int64, q_off [B_max+1] int64, status [1] int32): slot b's row rows[q_off[b] : q_off[b+1]] holds the
+    GLOBAL indices, ascending, of the points of scene cloud_ind[b] within radius of centers[b] (``ball_query``'s float64
+    test), for all slots in three launches. Rows that do not fit cap are dropped and status[0] is set to 1 (a given
+    status is left as it is otherwise). A cloud_ind outside the table is an empty slot. Nothing is read back."""
+    if not isinstance(res, TrainResident):
+        raise RuntimeError("sphere_members: a TrainResident expected")
+    cloud_ind, B_max = _slot_args("sphere_members", cloud_ind, centers)
+    dev, cap = cloud_ind.device, int(cap)
+    if status is None:
+        status = torch.zeros((1,), device=dev, dtype=torch.int32)
+    _dev(status)
+    if status.dtype != torch.int32 or status.numel() < 1:
+        raise RuntimeError("sphere_members: status must be an int32 tensor")
+    tile = SPHERE_CONSTANTS["MVK_SPHERE_TILE"]
+    block_counts = torch.empty((max(1, B_max * max(1, -(-res.max_points // tile))),), device=dev, dtype=torch.int32)
+    rows = torch.empty((cap,), device=dev, dtype=torch.int64)
+    q_off = torch.zeros((B_max + 1,), device=dev, dtype=torch.int64)
+    check(lib().mvk_sphere_members(_p(res.points), res.P, _p(res.table), res.S, res.NB, res.F, res.NW, _p(cloud_ind),
+                                   _p(centers), B_max, float(radius), res.max_points, cap, _p(block_counts), _p(rows),
+                                   _p(q_off), _p(status), _stream()))
+    return rows, q_off, status
+
+
+def sphere_select_frames(res, cloud_ind, mask_rows, mask_off, num_frames):
+    """sel [B_max, num_frames] int32, scene-local: the greedy frame choice of every slot on its own scene's bit rows, over
+    the base points found in the slot's mask row (``sphere_members`` with in_radius + mask_margin). An empty slot chooses
+    frame 0."""
+    if not isinstance(res, TrainResident):
+        raise RuntimeError("sphere_select_frames: a TrainResident expected")
+    _dev(cloud_ind, mask_rows, mask_off)
+    B_max = _slots("sphere_select_frames", cloud_ind.shape[0])
+    cloud_ind = _i64_vec(cloud_ind, B_max, "sphere_select_frames: cloud_ind")
+    mask_rows = _i64_vec(mask_rows, mask_rows.shape[0], "sphere_select_frames: mask_rows")
+    mask_off = _i64_vec(mask_off, B_max + 1, "sphere_select_frames: mask_off")
+    sel = torch.empty((B_max, int(num_frames)), device=cloud_ind.device, dtype=torch.int32)
+    check(lib().mvk_sphere_select_frames(_p(res.bits), res.NW, _p(res.base_point_ind), res.NB, _p(res.table), res.S, res.P,
+                                         res.F, _p(cloud_ind), _p(mask_rows), mask_rows.shape[0], _p(mask_off), B_max,
+                                         int(num_frames), res.max_base, res.max_frames, _p(sel), _stream()))
+    return sel
+
+
+def sphere_unproject(res, sel, cloud_ind, flips=None):
+    """``train_unproject`` for sphere slots: a sphere has no box, so the mask is depth > 0 alone -- the box handed on is
+    (-FLT_MAX, FLT_MAX), which no finite pixel leaves -- and image_xyz is not rotated. Returns (keys [B_max, nv*h*w, 3]
+    f64, image_xyz [B_max,nv,h,w,3] f32, image_mask [B_max,nv,h,w] bool, images [B_max,nv,3,h,w] f32, num_valid [B_max]
+    int32); flips [B_max,nv] uint8 / bool mirrors a view in all of them."""
+    big = float(_np.finfo(_np.float32).max)
+    box = torch.tensor([-big, -big, big, big], dtype=torch.float32).repeat(sel.shape[0], 1)
+    staged = torch.empty(tuple(box.shape), dtype=torch.float32, pin_memory=True).copy_(box)
+    return train_unproject(res, sel, cloud_ind, staged.to(sel.device, non_blocking=True), flips=flips)
+
+
+def sphere_batch_rows(sres, cloud_ind, centers, rows, q_off, R, scale, keep_color, knn, npix, noise=None):
+    """The batch's rows in one launch (ScanNet_sphere_color.py:605-616, :657-670): a dict of HBM tensors over the cap
+    slots of rows -- points [cap,3] f32 (centred in float64, rounded, then ((x0 R0j + x1 R1j) + x2 R2j) * scale_j +
+    noise_ij in float32), world [cap,3] f32 ((float)((double)points + (double)centre); column 2 is the height feature),
+    feat_aggre_points [cap,3] f32, colors [cap,3] f32 (times keep_color[b]), labels [cap] int64, input_inds [cap] int64
+    (scene-local), knn_stacked [cap,k] int64 (knn + b * npix, -1 staying -1). R [B_max,9] f32, scale [B_max,3] f32,
+    keep_color [B_max] f32 (0 or 1), noise [cap,3] f32 or None, all in HBM. Rows of no slot: zeros, -1 in the indices."""
+    res = _sphere_res("sphere_batch_rows", sres)
+    cloud_ind, B_max = _slot_args("sphere_batch_rows", cloud_ind, centers)
+    _dev(rows, q_off, R, scale, keep_color, knn, noise)
+    cap = rows.shape[0]
+    rows, q_off = _i64_vec(rows, cap, "sphere_batch_rows: rows"), _i64_vec(q_off, B_max + 1, "sphere_batch_rows: q_off")
+    for name, t, shape in (("R", R, (B_max, 9)), ("scale", scale, (B_max, 3)), ("keep_color", keep_color, (B_max,))) + \
+            ((("noise", noise, (cap, 3)),) if noise is not None else ()):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise RuntimeError("sphere_batch_rows: %s must be a contiguous float32 tensor of shape %s" % (name, shape))
+    if knn.dtype != torch.int64 or knn.dim() != 2 or knn.shape[0] != cap or not knn.is_contiguous():
+        raise RuntimeError("sphere_batch_rows: knn must be a contiguous int64 [cap, k] tensor")
+    k, dev = knn.shape[1], rows.device
+    f3 = lambda: torch.empty((cap, 3), device=dev, dtype=torch.float32)
+    out = dict(points=f3(), world=f3(), feat_aggre_points=f3(), colors=f3(),
+               labels=torch.empty((cap,), device=dev, dtype=torch.int64),
+               knn_stacked=torch.empty((cap, k), device=dev, dtype=torch.int64),
+               input_inds=torch.empty((cap,), device=dev, dtype=torch.int64))
+    check(lib().mvk_sphere_batch_rows(_p(res.points), _p(sres.colors), _p(res.labels), res.P, _p(res.table), res.S, res.NB,
+                                      res.F, res.NW, _p(cloud_ind), _p(centers), _p(rows), cap, _p(q_off), B_max, _p(R),
+                                      _p(scale), _p(noise), _p(keep_color), _p(knn), k, int(npix), _p(out["points"]),
+                                      _p(out["world"]), _p(out["feat_aggre_points"]), _p(out["colors"]), _p(out["labels"]),
+                                      _p(out["knn_stacked"]), _p(out["input_inds"]), _stream()))
+    return out
