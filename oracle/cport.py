@@ -71,6 +71,13 @@ def _ptr(a, t):
 
 
 def subsample_batch(points, lens, features=None, labels=None, dl=0.1, max_p=0, impl="oracle"):
+    """batch_grid_subsampling: (s_points, s_lens[, s_features][, s_labels]).
+
+    Two inputs must never reach impl="ref" -- the compiled reference core does not survive them:
+      * an empty cloud (a 0 in lens): it dies with SIGFPE;
+      * ldim = 2 (two label columns) in a batch of more than one cloud: it throws std::length_error (its class-slice
+        end iterator is only right for ldim == 1, grid_subsampling.cpp:157-158); a single cloud with ldim = 2 is fine.
+    The oracle runs both; for them it stands alone (tests/cloud_cases.py marks such cases reference=False)."""
     pts = _f32(points)
     lens = _i32(lens)
     N, B = pts.shape[0], lens.shape[0]
@@ -122,6 +129,11 @@ def subsample(points, features=None, labels=None, dl=0.1, impl="oracle"):
 
 
 def radius_neighbors_batch(queries, supports, q_lens, s_lens, radius, impl="oracle"):
+    """batch_nanoflann_neighbors: int32 [Nq, W], rows ascending in (d2, index), padded with Ns.
+
+    impl="ref" steps ONE cloud forward when a cloud's queries end (neighbors.cpp:272 is an `if`): after a cloud without
+    queries that is not the last one it searches every later query in the wrong cloud's supports. Its rows in front of
+    such a cloud are right, the rest is not a reference for anything (tests/cloud_cases.py: NbCase.ref_rows)."""
     q, s = _f32(queries), _f32(supports)
     ql, sl = _i32(q_lens), _i32(s_lens)
     Nq, Ns, B = q.shape[0], s.shape[0], ql.shape[0]

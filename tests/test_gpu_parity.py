@@ -60,6 +60,8 @@ def test_subsample_labels_vs_oracle_many_classes(ops):
 @pytest.mark.parametrize("n,dl,seed", [(1, 0.1, 0), (13, 0.5, 1), (14, 0.01, 2), (777, 0.05, 3),
                                         (20000, 0.04, 4), (200000, 0.03, 5)])
 def test_subsample_vs_oracle(ops, n, dl, seed):
+    # (13, ...) and (14, ...) count POINTS, not voxels: uniform clouds do not pin the unordered_map's rehash thresholds.
+    # Voxel counts at 13, 29, 59, ... +-1, voxel-edge, same-bucket and duplicate clouds: test_cloud_cases_gpu.py.
     from oracle import cport
     rng = np.random.default_rng(seed)
     p = (rng.random((n, 3)) * [3, 2, 1]).astype(np.float32)
