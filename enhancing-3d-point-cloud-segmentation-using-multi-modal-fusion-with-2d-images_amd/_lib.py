@@ -1,5 +1,5 @@
 """ctypes binding of libmvkpconv.so (C ABI: include/mvkpconv.h, with include/mvkpconv_scene.h,
-include/mvkpconv_train.h and include/mvkpconv_sphere.h beside it).
+include/mvkpconv_train.h, include/mvkpconv_sphere.h and include/mvkpconv_decoder.h beside it).
 
 There is NO fallback: if the HIP library is missing or stale this module raises. PyTorch is used
 only as the owner of device memory and streams -- every signature is plain pointers and sizes.
@@ -20,6 +20,7 @@ HEADER_PATH = os.path.join(_HERE, "..", "include", "mvkpconv.h")
 SCENE_HEADER_PATH = os.path.join(_HERE, "..", "include", "mvkpconv_scene.h")
 TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "mvkpconv_train.h")
 SPHERE_HEADER_PATH = os.path.join(_HERE, "..", "include", "mvkpconv_sphere.h")
+DECODER_HEADER_PATH = os.path.join(_HERE, "..", "include", "mvkpconv_decoder.h")
 
 # canonical C type -> ctypes type. A pointer that is not listed is POINTER(Structure) for a struct of the header and
 # c_void_p otherwise (device and host arrays alike are passed as addresses).
@@ -164,6 +165,13 @@ if (_sphere_structs
         or SPHERE_CONSTANTS.keys() & (CONSTANTS.keys() | SCENE_CONSTANTS.keys() | TRAIN_CONSTANTS.keys())):
     raise ValueError("mvkpconv_sphere.h: it may declare neither a struct nor a name of the other three headers")
 _SPHERE_PROTOTYPES = _bind(SPHERE_FUNCTIONS, {})[1]
+
+# the fifth header (the decoder's unary layers as two products, csrc/gemm.hip): the same again, functions only
+DECODER_FUNCTIONS, _decoder_structs, _decoder_constants = parse_header(_read_header(DECODER_HEADER_PATH, "mvkpconv_decoder.h"))
+if (_decoder_structs or _decoder_constants
+        or DECODER_FUNCTIONS.keys() & (FUNCTIONS.keys() | SCENE_FUNCTIONS.keys() | TRAIN_FUNCTIONS.keys() | SPHERE_FUNCTIONS.keys())):
+    raise ValueError("mvkpconv_decoder.h: it may declare neither a struct, a constant nor a name of the other four headers")
+_DECODER_PROTOTYPES = _bind(DECODER_FUNCTIONS, {})[1]
 BnFwdProblem, BnBwdProblem = _CLASSES["mvk_bn_fwd_problem"], _CLASSES["mvk_bn_bwd_problem"]
 BnFinish, ATransform = _CLASSES["mvk_bn_finish"], _CLASSES["mvk_a_transform"]
 RevList, RegLayer = _CLASSES["mvk_rev_list"], _CLASSES["mvk_reg_layer"]
@@ -203,7 +211,7 @@ def lib():
                 "no CPU fallback for the MV-KPConv hot path." % LIB_PATH)
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in list(_PROTOTYPES.items()) + list(_SCENE_PROTOTYPES.items()) + list(_TRAIN_PROTOTYPES.items()) \
-                + list(_SPHERE_PROTOTYPES.items()):
+                + list(_SPHERE_PROTOTYPES.items()) + list(_DECODER_PROTOTYPES.items()):
             fn = getattr(l, name)          # AttributeError = missing export = stale build: loud
             fn.restype = res
             fn.argtypes = args

@@ -1,5 +1,5 @@
 """Builds libmvkpconv.so (the C-ABI HIP library, include/mvkpconv.h, include/mvkpconv_scene.h, include/mvkpconv_train.h and
-include/mvkpconv_sphere.h) in-tree for gfx950.
+include/mvkpconv_sphere.h, include/mvkpconv_decoder.h) in-tree for gfx950.
 
 hipcc cross-compiles without a GPU; the built .so is git-ignored but travels to the GPU box.
 Usage:  python <pkg>/build.py [--force]
@@ -61,6 +61,7 @@ def build_library(force=False, verbose=False):
     common = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "blockscan.h"), os.path.join(CSRC, "compact.h"),
               os.path.join(CSRC, "pn2_rows.h"), os.path.join(CSRC, "unproject.h"), os.path.join(CSRC, "select_frames.h"),
               os.path.join(CSRC, "knn_core.h"), os.path.join(HERE, "..", "include", "mvkpconv_sphere.h"),
+              os.path.join(HERE, "..", "include", "mvkpconv_decoder.h"),
               os.path.join(HERE, "..", "include", "mvkpconv.h"), os.path.join(HERE, "..", "include", "mvkpconv_scene.h"),
               os.path.join(HERE, "..", "include", "mvkpconv_train.h"),
               os.path.join(HERE, "..", "include", "mvk_prime_list.h"), os.path.abspath(__file__)]

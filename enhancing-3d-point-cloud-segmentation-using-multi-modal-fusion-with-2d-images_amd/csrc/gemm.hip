@@ -29,9 +29,11 @@
 #include <stdlib.h>
 
 #include <mutex>
+#include <vector>
 #include <type_traits>
 
 #include "common.h"
+#include "../../include/mvkpconv_decoder.h"
 
 namespace {
 
@@ -286,11 +288,22 @@ struct GemmArgs {
   float ax_slope;
   const int32_t* ax_nvalid;
   float* ax_out;
+  // rows of C are ldc floats apart (>= N): C may be a column window of a wider matrix -- the two slabs of the decoder's
+  // weight gradient dW = [G_c^T x_c | g^T skip] are two products into one tensor. Every store, atomic and accumulate honours it.
+  int64_t ldc;
+  // row-gathered addend (ADD instantiations; null add_src: off): row m of the product gets + add_src[add_idx[m * add_stride], :]
+  // (add_src [add_ns, N] dense; an index outside [0, add_ns) -- the shadow row -- adds nothing) BEFORE bias, the statistics
+  // epilogue and the finish: y = skip . W2^T + (x_c . W1^T)[idx], the decoder's unary layer without its concatenation.
+  // Exactly one contributor adds it: the tile itself, split 0 of an atomic split, the last arriver of an ordered one.
+  const float* add_src;
+  const void* add_idx;
+  int add_idx64;
+  int64_t add_stride, add_ns;
 };
 
 constexpr int XF_KMAX = 512;     // longest k-range of one workgroup with an A-operand transform (LDS table of 4 floats per k)
 
-template <bool TA, bool TB, int PM, int QN, int WM, int WN, bool DUAL = false, bool XF = false>
+template <bool TA, bool TB, int PM, int QN, int WM, int WN, bool DUAL = false, bool XF = false, bool ADD = false>
 __device__ __forceinline__ void gemm_body(const GemmArgs& a, const int bx, const int by, const int bz) {
   static_assert(WM * WN == 4, "four waves per workgroup");
   constexpr int TM = 16 * PM * WM, TN = 16 * QN * WN;
@@ -500,6 +513,29 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& a, const int bx, const
 
   // C/D map of the 16 x 16 MFMA: col = lane & 15, row = 4 (lane >> 4) + reg
   const int ci = lane & 15, g4 = (lane >> 4) * 4;
+  if constexpr (ADD) {
+    // the row-gathered addend, once per output element: here every split of an ordered reduction has already been summed
+    // (only the last arriver gets this far); of an atomic split, split 0 carries it
+    if (a.add_src && (a.det_ws || bz == 0)) {
+#pragma unroll
+      for (int p = 0; p < PM; ++p)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int64_t row = m0 + ra + 16 * p + g4 + r;
+          if (row < a.M) {
+            const int j = a.add_idx64 ? load_idx<true>(a.add_idx, row * a.add_stride, a.add_ns)
+                                      : load_idx<false>(a.add_idx, row * a.add_stride, a.add_ns);
+            if (j >= 0) {
+#pragma unroll
+              for (int q = 0; q < QN; ++q) {
+                const int64_t col = n0 + rb + 16 * q + ci;
+                if (col < a.N) acc[p][q][r] += a.add_src[(int64_t)j * a.N + col];
+              }
+            }
+          }
+        }
+    }
+  }
 #pragma unroll
   for (int q = 0; q < QN; ++q) {
     const int64_t col = n0 + rb + 16 * q + ci;
@@ -524,7 +560,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& a, const int bx, const
               }
               continue;
             }
-            float* c = a.C + row * a.N + col;
+            float* c = a.C + row * a.ldc + col;
             if (a.atomic_out)
               atomicAdd(c, acc[p][q][r]);
             else if (a.accumulate)
@@ -717,16 +753,24 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_xf(const GemmArgs a) {
   gemm_body<false, TB, PM, 1, 1, 4, false, true>(a, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
-// Two independent products of the same operand layout, tile shape and row count in one launch: their column tiles side
-// by side along blockIdx.x, each with its own split of the reduction (workgroups beyond a product's split leave at once).
-// unary1 and the shortcut layer of a bottleneck block read the same input (blocks.py:596-649).
+// the NT product with the row-gathered addend (GemmArgs add_*): the plan's four tile shapes
+template <int PM, int QN, int WM, int WN>
+__global__ __launch_bounds__(256) void gemm_f32_mfma_add(const GemmArgs a) {
+  gemm_body<false, true, PM, QN, WM, WN, false, false, true>(a, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+
+// Two independent products of the same operand layout and tile shape in one launch: their column tiles side by side along
+// blockIdx.x, each with its own row count and its own split of the reduction (workgroups beyond a product's row tiles or
+// split leave at once). unary1 and the shortcut layer of a bottleneck block read the same input (blocks.py:596-649); the
+// two halves of the decoder's feature gradient (coarse rows and fine rows) read the same weights.
 template <bool TA, bool TB, int PM, int QN, int WM, int WN>
-__global__ __launch_bounds__(256) void gemm_f32_mfma_pair(const GemmArgs a0, const GemmArgs a1, int gx0, int gz0, int gz1) {
+__global__ __launch_bounds__(256) void gemm_f32_mfma_pair(const GemmArgs a0, const GemmArgs a1, int gx0, int gy0, int gy1,
+                                                          int gz0, int gz1) {
   if ((int)blockIdx.x < gx0) {
-    if ((int)blockIdx.z >= gz0) return;
+    if ((int)blockIdx.z >= gz0 || (int)blockIdx.y >= gy0) return;
     gemm_body<TA, TB, PM, QN, WM, WN>(a0, blockIdx.x, blockIdx.y, blockIdx.z);
   } else {
-    if ((int)blockIdx.z >= gz1) return;
+    if ((int)blockIdx.z >= gz1 || (int)blockIdx.y >= gy1) return;
     gemm_body<TA, TB, PM, QN, WM, WN>(a1, blockIdx.x - gx0, blockIdx.y, blockIdx.z);
   }
 }
@@ -937,15 +981,17 @@ bool launch_cfg(const Plan& p, dim3 grid, hipStream_t st, const GemmArgs& a) {
 }
 
 template <bool TA, bool TB, int PM>
-void launch_pair_one(dim3 grid, hipStream_t st, const GemmArgs& a0, const GemmArgs& a1, int gx0, int gz0, int gz1) {
-  hipLaunchKernelGGL((gemm_f32_mfma_pair<TA, TB, PM, 1, 1, 4>), grid, dim3(256), 0, st, a0, a1, gx0, gz0, gz1);
+void launch_pair_one(dim3 grid, hipStream_t st, const GemmArgs& a0, const GemmArgs& a1, int gx0, int gy0, int gy1, int gz0,
+                     int gz1) {
+  hipLaunchKernelGGL((gemm_f32_mfma_pair<TA, TB, PM, 1, 1, 4>), grid, dim3(256), 0, st, a0, a1, gx0, gy0, gy1, gz0, gz1);
 }
 
 template <bool TA, bool TB>
-bool launch_pair_cfg(const Plan& p, dim3 grid, hipStream_t st, const GemmArgs& a0, const GemmArgs& a1, int gx0, int gz0, int gz1) {
+bool launch_pair_cfg(const Plan& p, dim3 grid, hipStream_t st, const GemmArgs& a0, const GemmArgs& a1, int gx0, int gy0, int gy1,
+                     int gz0, int gz1) {
   if (p.qn != 1) return false;
-  if (p.pm == 2) return launch_pair_one<TA, TB, 2>(grid, st, a0, a1, gx0, gz0, gz1), true;
-  if (p.pm == 4) return launch_pair_one<TA, TB, 4>(grid, st, a0, a1, gx0, gz0, gz1), true;
+  if (p.pm == 2) return launch_pair_one<TA, TB, 2>(grid, st, a0, a1, gx0, gy0, gy1, gz0, gz1), true;
+  if (p.pm == 4) return launch_pair_one<TA, TB, 4>(grid, st, a0, a1, gx0, gy0, gy1, gz0, gz1), true;
   return false;
 }
 
@@ -979,7 +1025,7 @@ KSplit clamp_split(int64_t Kd, int split) {
 GemmArgs make_args(const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t Kd, int64_t lda, int64_t ldb,
                    KSplit ks) {
   GemmArgs a{};
-  a.A = A; a.B = B; a.C = C; a.M = M; a.N = N; a.Kd = Kd;
+  a.A = A; a.B = B; a.C = C; a.M = M; a.N = N; a.Kd = Kd; a.ldc = N;
   a.lda = lda; a.ldb = ldb; a.vecA = vec_width(A, lda); a.vecB = vec_width(B, ldb);
   a.k_per_split = ks.k_per_split; a.atomic_out = ks.n > 1; a.det_nsplit = ks.n;
   a.act_slope = 1.f; a.ax_slope = 1.f; a.vecA2 = 1; a.vecB2 = 1; a.seg_shift = -1;      // the neutral values that are not zero
@@ -1008,6 +1054,14 @@ struct ScatterOut {
 };
 
 // what a single product may ask for beyond C = op(A) . op(B); every extern "C" wrapper names the few fields it sets
+// the row-gathered addend of GemmArgs as an entry point hands it over
+struct RowAddend {
+  const float* src;
+  const void* idx;
+  int idx64;
+  int64_t stride, ns;
+};
+
 struct GemmOpts {
   int accumulate = 0, split_k = 0;
   float* bn_part = nullptr;
@@ -1017,6 +1071,8 @@ struct GemmOpts {
   const ScatterOut* scatter = nullptr;
   int seg_shift = -1;
   int64_t seg_extra = 0, ldb = 0, lda = 0;     // lda: A = a row (column, when transposed) block of a taller matrix
+  int64_t ldc = 0;                             // C = a column window of a wider matrix (0: dense)
+  const RowAddend* add = nullptr;
   const mvk_bn_finish* fin = nullptr;
   const mvk_a_transform* ax = nullptr;
 };
@@ -1028,7 +1084,10 @@ int gemm_run(const float* A, const float* B, float* C, int64_t M, int64_t N, int
   if (M == 0 || N == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   MVK_REQUIRE(!(o.bn_part && (o.accumulate || Kd == 0)), "gemm: BatchNorm statistics need a plain store of a non-empty product");
+  MVK_REQUIRE(o.ldc <= 0 || o.ldc >= N, "gemm: ldc < N");
+  const int64_t ldc = o.ldc > 0 ? o.ldc : N;
   if (Kd == 0) {
+    MVK_REQUIRE(ldc == N && !o.add, "gemm: an empty reduction into a column window or with an addend");
     if (!o.accumulate && o.split_k <= 1) MVK_CHECK_HIP(hipMemsetAsync(C, 0, sizeof(float) * M * N, st));
     return 0;
   }
@@ -1041,14 +1100,14 @@ int gemm_run(const float* A, const float* B, float* C, int64_t M, int64_t N, int
   // statistics epilogue and its consumers stop far below such row counts. A chunk is a whole number of every row tile
   // (16 .. 256 rows) and stays below 2^16 tiles of the smallest.
   if (cdiv64(M, p.tm()) >= 65536) {
-    MVK_REQUIRE(!o.bn_part && !o.fin && !o.ax && !o.scatter && o.seg_shift < 0 && ks.n < 65536, "gemm: grid too large");
+    MVK_REQUIRE(!o.bn_part && !o.fin && !o.ax && !o.scatter && !o.add && o.seg_shift < 0 && ks.n < 65536, "gemm: grid too large");
     constexpr int64_t CHUNK = 15 * 65536;
     GemmOpts oc = o;
     oc.split_k = ks.n;
     oc.lda = lda;
     for (int64_t m0 = 0; m0 < M; m0 += CHUNK) {
       const int64_t mc = M - m0 < CHUNK ? M - m0 : CHUNK;
-      if (int e = gemm_run(A + (transA ? m0 : m0 * lda), B, C + m0 * N, mc, N, Kd, transA, transB, oc, stream)) return e;
+      if (int e = gemm_run(A + (transA ? m0 : m0 * lda), B, C + m0 * ldc, mc, N, Kd, transA, transB, oc, stream)) return e;
     }
     return 0;
   }
@@ -1059,7 +1118,7 @@ int gemm_run(const float* A, const float* B, float* C, int64_t M, int64_t N, int
     a.vecB = ((uintptr_t)B % 16 == 0 && o.seg_extra % 4 == 0) ? 4 : 1;
   }
   a.accumulate = o.accumulate; a.bn_part = o.bn_part; a.n_valid = o.n_valid; a.bias = o.bias; a.act_slope = o.act_slope;
-  a.seg_shift = o.seg_shift; a.seg_extra = o.seg_extra;
+  a.seg_shift = o.seg_shift; a.seg_extra = o.seg_extra; a.ldc = ldc;
   if (o.scatter) {
     a.sc_idx = o.scatter->idx; a.sc_idx64 = o.scatter->idx64; a.sc_c1 = o.scatter->c1; a.sc_stride = o.scatter->stride;
     a.sc_ns = o.scatter->ns; a.sc_dst = o.scatter->dst; a.sc_rest = o.scatter->rest;
@@ -1071,13 +1130,25 @@ int gemm_run(const float* A, const float* B, float* C, int64_t M, int64_t N, int
   if (int e = set_finish(a, o.fin, grid.y)) return e;
   if (const mvk_a_transform* ax = o.ax) {
     // the consumer's half of a folded BatchNorm (GemmArgs (b)): wide NT tiles, the workgroup's k-range inside the table
-    MVK_REQUIRE(!transA && transB && !p.narrow && p.qn == 1 && (p.pm == 2 || p.pm == 4) && ks.k_per_split <= XF_KMAX && !o.scatter &&
+    MVK_REQUIRE(!transA && transB && !p.narrow && p.qn == 1 && (p.pm == 2 || p.pm == 4) && ks.k_per_split <= XF_KMAX && !o.scatter && !o.add &&
                     o.seg_shift < 0 && ax->mean && ax->invstd && ax->gamma && ax->beta && ax->slope > 0.f,
                 "gemm: the operand transform needs an NT product of more than 32 columns with k-ranges <= %d", XF_KMAX);
     a.ax_mean = ax->mean; a.ax_invstd = ax->invstd; a.ax_gamma = ax->gamma; a.ax_beta = ax->beta; a.ax_slope = ax->slope;
     a.ax_nvalid = ax->n_valid; a.ax_out = ax->out;
     if (p.pm == 2) hipLaunchKernelGGL((gemm_f32_mfma_xf<true, 2>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((gemm_f32_mfma_xf<true, 4>), grid, dim3(256), 0, st, a);
+    MVK_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
+  if (const RowAddend* ad = o.add) {
+    MVK_REQUIRE(!transA && transB && !o.scatter && !o.accumulate && o.seg_shift < 0 && ad->src && ad->idx && ad->stride >= 1 && ad->ns >= 0,
+                "gemm: the row-gathered addend needs an NT product with a plain store, a source and an index");
+    a.add_src = ad->src; a.add_idx = ad->idx; a.add_idx64 = ad->idx64; a.add_stride = ad->stride; a.add_ns = ad->ns;
+    if (p.narrow && p.pm == 1 && p.qn == 1) hipLaunchKernelGGL((gemm_f32_mfma_add<1, 1, 4, 1>), grid, dim3(256), 0, st, a);
+    else if (p.narrow && p.pm == 1 && p.qn == 2) hipLaunchKernelGGL((gemm_f32_mfma_add<1, 2, 4, 1>), grid, dim3(256), 0, st, a);
+    else if (!p.narrow && p.pm == 2 && p.qn == 1) hipLaunchKernelGGL((gemm_f32_mfma_add<2, 1, 1, 4>), grid, dim3(256), 0, st, a);
+    else if (!p.narrow && p.pm == 4 && p.qn == 1) hipLaunchKernelGGL((gemm_f32_mfma_add<4, 1, 1, 4>), grid, dim3(256), 0, st, a);
+    else MVK_REQUIRE(false, "gemm: no addend kernel for plan pm=%d qn=%d narrow=%d", p.pm, p.qn, p.narrow);
     MVK_CHECK_HIP(hipGetLastError());
     return 0;
   }
@@ -1117,11 +1188,20 @@ int gemm_pair_run(const float* A, const float* B0, const float* B1, float* C0, f
   if (int e = set_finish(a0, fin0, gy)) return e;
   if (int e = set_finish(a1, fin1, gy)) return e;
   dim3 grid((unsigned)(gx0 + gx1), (unsigned)gy, (unsigned)(s0.n > s1.n ? s0.n : s1.n));
-  const bool ok = transB ? launch_pair_cfg<false, true>(p0, grid, st, a0, a1, gx0, s0.n, s1.n)
-                         : launch_pair_cfg<false, false>(p0, grid, st, a0, a1, gx0, s0.n, s1.n);
+  const bool ok = transB ? launch_pair_cfg<false, true>(p0, grid, st, a0, a1, gx0, (int)gy, (int)gy, s0.n, s1.n)
+                         : launch_pair_cfg<false, false>(p0, grid, st, a0, a1, gx0, (int)gy, (int)gy, s0.n, s1.n);
   MVK_REQUIRE(ok, "gemm pair: no kernel for plan pm=%d", p0.pm);
   MVK_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+// whether C0 [M0,N0] = A0 . B0 and C1 [M1,N1] = A1 . B1 (NN, one reduction length) can share a launch: both on the wide tile
+// class with the plan's own 32-row tile
+bool nn_pair_plans(int64_t M0, int64_t N0, int64_t M1, int64_t N1, int64_t Kd, Plan& p0, Plan& p1) {
+  if (M0 <= 0 || N0 <= 0 || M1 <= 0 || N1 <= 0 || Kd <= 0) return false;
+  p0 = plan_gemm(M0, N0, Kd, 0, false);
+  p1 = plan_gemm(M1, N1, Kd, 0, false);
+  return !p0.narrow && !p1.narrow && p0.pm == p1.pm && p0.qn == 1 && p1.qn == 1 && (p0.pm == 2 || p0.pm == 4);
 }
 
 }  // namespace
@@ -1283,6 +1363,69 @@ extern "C" int mvk_gemm_f32_ldb(const float* A, const float* B, float* C, int64_
   return gemm_run(A, B, C, M, N, Kd, 0, 0, o, stream);
 }
 
+// C [M,N] = A [M,Kd] . B[:, col0:col0+Kd]^T for a row-major B [N, ldb] read in place (a column block of a wider weight
+// matrix, no copy) + the optional row-gathered addend add_src[add_idx[m * add_stride], :] (add_src [add_ns, N]; null: none;
+// an index outside [0, add_ns) adds nothing), then the optional statistics epilogue / finish exactly as mvk_gemm_f32_bn
+// (same plan decision: mvk_gemm_f32_plan(M, N, Kd, 0, bn_part != null)). The decoder's unary layer as two products:
+// Yc = x_c . W[:, :C1]^T at coarse rows, y = skip . W[:, C1:]^T + Yc[idx].
+extern "C" int mvk_gemm_f32_nt_ldb_add(const float* A, const float* B, int64_t col0, int64_t ldb, float* C, int64_t M, int64_t N,
+                                       int64_t Kd, const float* add_src, const void* add_idx, int add_idx64,
+                                       int64_t add_stride, int64_t add_ns, float* bn_part, const int32_t* n_valid,
+                                       const void* fin /* const mvk_bn_finish* */, void* stream) {
+  MVK_REQUIRE(M > 0 && N > 0 && Kd > 0 && col0 >= 0 && ldb >= col0 + Kd, "gemm nt_ldb_add: empty product or a column block outside B");
+  MVK_REQUIRE((add_src == nullptr) == (add_idx == nullptr), "gemm nt_ldb_add: the addend needs its source and its index");
+  const RowAddend ad{add_src, add_idx, add_idx64, add_stride, add_ns};
+  GemmOpts o; o.ldb = ldb; o.bn_part = bn_part; o.n_valid = n_valid; o.fin = (const mvk_bn_finish*)fin; o.add = add_src ? &ad : nullptr;
+  return gemm_run(A, B + col0, C, M, N, Kd, 0, 1, o, stream);
+}
+
+// C[:, 0:N] = A^T . B for A [Kd,M], B [Kd,N] row-major and C a column window of a wider row-major matrix (rows ldc >= N
+// floats apart): one slab of a weight gradient that is the sum of no single product (atomics into a zero-initialised
+// window when mvk_gemm_f32_plan(M, N, Kd) splits and no arena is set). Columns outside the window are not touched.
+extern "C" int mvk_gemm_f32_tn_ldc(const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t Kd, int64_t ldc,
+                                   void* stream) {
+  MVK_REQUIRE(ldc >= N && Kd > 0, "gemm tn_ldc: ldc < N or an empty reduction");
+  GemmOpts o; o.ldc = ldc;
+  return gemm_run(A, B, C, M, N, Kd, 1, 0, o, stream);
+}
+
+// out[0] = 1 when mvk_gemm_f32_nn_pair can run the two products in one launch (both outputs wider than 32 columns),
+// out[1..2] = the splits of the two reductions (zero-initialise an output whose split is > 1 unless an arena is set)
+extern "C" int mvk_gemm_f32_nn_pair_plan(int64_t M0, int64_t N0, int64_t M1, int64_t N1, int64_t Kd, int* out /* [3] */) {
+  MVK_REQUIRE(M0 >= 0 && N0 >= 0 && M1 >= 0 && N1 >= 0 && Kd >= 0 && out, "gemm nn pair plan: bad arguments");
+  out[0] = out[1] = out[2] = 0;
+  Plan p0, p1;
+  if (!nn_pair_plans(M0, N0, M1, N1, Kd, p0, p1)) return 0;
+  out[0] = 1;
+  out[1] = clamp_split(Kd, p0.split).n;
+  out[2] = clamp_split(Kd, p1.split).n;
+  return 0;
+}
+
+// C0 [M0,N0] = A0 [M0,Kd] . B0 and C1 [M1,N1] = A1 [M1,Kd] . B1 in ONE launch, B0 / B1 [Kd, *] column blocks of row-major
+// matrices whose rows are ldb floats apart: two products of DIFFERENT row counts (workgroups beyond a product's own row
+// tiles leave at once) -- dx_c = G_c . W[:, :C1] at coarse rows and d_skip = g . W[:, C1:] at fine rows.
+extern "C" int mvk_gemm_f32_nn_pair(const float* A0, const float* B0, float* C0, int64_t M0, int64_t N0, const float* A1,
+                                    const float* B1, float* C1, int64_t M1, int64_t N1, int64_t Kd, int64_t ldb, void* stream) {
+  Plan p0, p1;
+  MVK_REQUIRE(nn_pair_plans(M0, N0, M1, N1, Kd, p0, p1) && ldb >= N0 && ldb >= N1,
+              "gemm nn pair: the two products do not share a tile shape (ask mvk_gemm_f32_nn_pair_plan first)");
+  hipStream_t st = (hipStream_t)stream;
+  const KSplit s0 = clamp_split(Kd, p0.split), s1 = clamp_split(Kd, p1.split);
+  GemmArgs a0 = make_args(A0, B0, C0, M0, N0, Kd, Kd, ldb, s0);
+  GemmArgs a1 = make_args(A1, B1, C1, M1, N1, Kd, Kd, ldb, s1);
+  const int64_t tm = p0.tm(), tn = p0.tn(), gy0 = cdiv64(M0, tm), gy1 = cdiv64(M1, tm);
+  MVK_REQUIRE(gy0 < 65536 && gy1 < 65536 && s0.n < 65536 && s1.n < 65536, "gemm: grid too large");
+  const int gx0 = (int)cdiv64(N0, tn), gx1 = (int)cdiv64(N1, tn);
+  MVK_ORDERED(make_ordered(st, a0, s0.n, gx0, gy0, tm, tn));
+  MVK_ORDERED(make_ordered(st, a1, s1.n, gx1, gy1, tm, tn));
+  dim3 grid((unsigned)(gx0 + gx1), (unsigned)(gy0 > gy1 ? gy0 : gy1), (unsigned)(s0.n > s1.n ? s0.n : s1.n));
+  const bool ok = launch_pair_cfg<false, false>(p0, grid, st, a0, a1, gx0, (int)gy0, (int)gy1, s0.n, s1.n);
+  MVK_REQUIRE(ok, "gemm nn pair: no kernel for plan pm=%d", p0.pm);
+  MVK_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 // [d_x | d_skip] = A [M,Kd] . B [Kd,N] where the product is the gradient of cat([x[idx[m,0]], skip[m]]) (decoder:
 // closest_pool + torch.cat + nn.Linear, architectures.py:334-335): the first c1 columns are scattered onto d_x [Ns,c1]
 // (f32 atomics, zero-initialised by the caller), the others written to d_skip [M, N-c1] (atomics into a zero-initialised
@@ -1302,6 +1445,13 @@ struct MvkGemmProblem {
   const float* B;
   float* C;
   int64_t M, N, Kd;
+};
+// The same with an output leading dimension (56 bytes): C a column window of a wider matrix, rows ldc >= N floats apart.
+struct MvkGemmProblemLdc {
+  const float* A;
+  const float* B;
+  float* C;
+  int64_t M, N, Kd, ldc;
 };
 
 extern "C" int64_t mvk_gemm_group_entry_bytes(void) { return (int64_t)sizeof(GroupEntry); }
@@ -1342,11 +1492,11 @@ extern "C" int mvk_gemm_f32_tn_grouped_split(int64_t M, int64_t N, int64_t Kd) {
 
 // Fills `table_host` (n * mvk_gemm_group_entry_bytes() bytes, narrow problems first) for the device-side grouped launch
 // and reports how many of the problems are narrow (N <= 32) and the workgroup counts of the two launches.
-extern "C" int mvk_gemm_f32_tn_grouped_plan(const void* problems, int n, void* table_host, int* n_narrow,
-                                            int64_t* wgs_narrow, int64_t* wgs_wide, int32_t* splits /* [n] out */,
-                                            void* stream /* the stream mvk_gemm_f32_tn_grouped will launch on */) {
+extern "C" int mvk_gemm_f32_tn_grouped_plan_ldc(const void* problems, int n, void* table_host, int* n_narrow,
+                                                int64_t* wgs_narrow, int64_t* wgs_wide, int32_t* splits /* [n] out */,
+                                                void* stream /* the stream mvk_gemm_f32_tn_grouped will launch on */) {
   MVK_REQUIRE(n >= 0 && problems && table_host && n_narrow && wgs_narrow && wgs_wide && splits, "grouped gemm: bad arguments");
-  const MvkGemmProblem* pr = (const MvkGemmProblem*)problems;
+  const MvkGemmProblemLdc* pr = (const MvkGemmProblemLdc*)problems;
   GroupEntry* tab = (GroupEntry*)table_host;
   int nn = 0;
   for (int i = 0; i < n; ++i) nn += pr[i].N <= 32 ? 1 : 0;
@@ -1361,14 +1511,16 @@ extern "C" int mvk_gemm_f32_tn_grouped_plan(const void* problems, int n, void* t
     ktiles = t < GROUP_KTILES_MIN ? GROUP_KTILES_MIN : (t > GROUP_KTILES_MAX ? GROUP_KTILES_MAX : (int)t);
   }
   for (int i = 0; i < n; ++i) {
-    const MvkGemmProblem& q = pr[i];
+    const MvkGemmProblemLdc& q = pr[i];
     MVK_REQUIRE(q.M > 0 && q.N > 0 && q.Kd > 0 && q.A && q.B && q.C, "grouped gemm: empty problem %d", i);
     const bool narrow = q.N <= 32;
     MVK_REQUIRE(!narrow || q.N > 16, "grouped gemm: outputs of <= 16 columns are not grouped");
+    MVK_REQUIRE(q.ldc >= q.N, "grouped gemm: ldc < N in problem %d", i);
     const KSplit ks = clamp_split(q.Kd, grouped_split_at(q.M, q.N, q.Kd, ktiles));
     const int split = ks.n;
     GroupEntry e{};
     e.args = make_args(q.A, q.B, q.C, q.M, q.N, q.Kd, q.M, q.N, ks);      // TN: A [Kd,M], B [Kd,N]
+    e.args.ldc = q.ldc;
     const int64_t tm = narrow ? 64 : 16 * group_wide_pm(), tn = narrow ? 32 : 64;      // plan tiles: narrow (pm 1, qn 2), wide (pm 2, qn 1)
     e.gx = (int)cdiv64(q.N, tn);
     e.gy = (int)cdiv64(q.M, tm);
@@ -1391,6 +1543,18 @@ extern "C" int mvk_gemm_f32_tn_grouped_plan(const void* problems, int n, void* t
   *wgs_narrow = wn;
   *wgs_wide = ww;
   return 0;
+}
+
+// the plan for dense outputs (records without ldc)
+extern "C" int mvk_gemm_f32_tn_grouped_plan(const void* problems, int n, void* table_host, int* n_narrow,
+                                            int64_t* wgs_narrow, int64_t* wgs_wide, int32_t* splits /* [n] out */,
+                                            void* stream) {
+  MVK_REQUIRE(n >= 0 && problems, "grouped gemm: bad arguments");
+  const MvkGemmProblem* pr = (const MvkGemmProblem*)problems;
+  std::vector<MvkGemmProblemLdc> v((size_t)n);
+  for (int i = 0; i < n; ++i) v[i] = MvkGemmProblemLdc{pr[i].A, pr[i].B, pr[i].C, pr[i].M, pr[i].N, pr[i].Kd, pr[i].N};
+  static const MvkGemmProblemLdc none{};
+  return mvk_gemm_f32_tn_grouped_plan_ldc(n > 0 ? v.data() : &none, n, table_host, n_narrow, wgs_narrow, wgs_wide, splits, stream);
 }
 
 // Launches the table prepared by mvk_gemm_f32_tn_grouped_plan (now in DEVICE memory): at most two launches.

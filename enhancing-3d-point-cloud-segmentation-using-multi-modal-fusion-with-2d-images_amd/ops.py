@@ -612,9 +612,9 @@ def flush_deferred(items, stream=None):
         return
     if stream is None or stream == torch.cuda.current_stream():
         return _flush_deferred(items)
-    for (A, B, _, _, _) in items:
-        A.record_stream(stream)
-        B.record_stream(stream)
+    for it in items:
+        it[0].record_stream(stream)
+        it[1].record_stream(stream)
     with torch.cuda.stream(stream):
         _flush_deferred(items)
 
@@ -636,8 +636,9 @@ def _flush_deferred(items=None):
     import numpy as np
     dev = items[0][0].device
     n = len(items)
-    prob = np.zeros(n, dtype=np.dtype([("A", "<u8"), ("B", "<u8"), ("C", "<u8"), ("M", "<i8"), ("N", "<i8"), ("Kd", "<i8")]))
-    for i, (A, B, out_ptr, _, storage) in enumerate(items):
+    prob = np.zeros(n, dtype=np.dtype([("A", "<u8"), ("B", "<u8"), ("C", "<u8"), ("M", "<i8"), ("N", "<i8"), ("Kd", "<i8"),
+                                       ("ldc", "<i8")]))
+    for i, (A, B, out_ptr, _, storage, ldc) in enumerate(items):
         if _storage_use_count(storage) < 2:
             # nothing but this list still owns the result: autograd did not adopt it as a .grad (it added the not yet
             # computed tensor to an existing gradient, or dropped it) -- the product would be lost silently
@@ -645,7 +646,7 @@ def _flush_deferred(items=None):
                                "grouped launch computed it; was the backward run on parameters that already hold a "
                                ".grad, or with hooks that copy gradients? Run it without the scope (MVK_DEFER_DW=0)"
                                % (A.shape[1], B.shape[1]))
-        prob[i] = (A.data_ptr(), B.data_ptr(), out_ptr, A.shape[1], B.shape[1], A.shape[0])
+        prob[i] = (A.data_ptr(), B.data_ptr(), out_ptr, A.shape[1], B.shape[1], A.shape[0], ldc)
     slots = _defer_slots(dev)
     if torch.cuda.is_current_stream_capturing():
         if len(slots) <= 2:
@@ -659,7 +660,7 @@ def _flush_deferred(items=None):
             slot["event"].synchronize()
     nn, wn, ww = C.c_int(0), C.c_int64(0), C.c_int64(0)
     splits = np.zeros(n, np.int32)
-    check(lib().mvk_gemm_f32_tn_grouped_plan(prob.ctypes.data_as(C.c_void_p), n, C.c_void_p(slot["host"].data_ptr()),
+    check(lib().mvk_gemm_f32_tn_grouped_plan_ldc(prob.ctypes.data_as(C.c_void_p), n, C.c_void_p(slot["host"].data_ptr()),
                                              C.byref(nn), C.byref(wn), C.byref(ww), splits.ctypes.data_as(C.c_void_p),
                                              _stream()))
     for i, item in enumerate(items):
@@ -681,10 +682,17 @@ def _accumulate_in_place_ok(t):
     been RECORDED (defer_weight_grads): mutating it first would corrupt that product silently. Not provably
     exclusive -> the caller computes `product + t` instead."""
     if _DEFER["on"] and _DEFER["items"]:
-        st = t.untyped_storage().data_ptr()
+        # by the bytes the tensors occupy, not by their storages: slices of the zero arena share ONE storage (an operand
+        # drawn from it -- the decoder's G_c -- must not make every other arena slice look like an operand)
+        if not t.is_contiguous():
+            return False
+        lo = t.data_ptr()
+        hi = lo + t.numel() * t.element_size()
         for it in _DEFER["items"]:
-            if it[0].untyped_storage().data_ptr() == st or it[1].untyped_storage().data_ptr() == st:
-                return False
+            for op in (it[0], it[1]):
+                a = op.data_ptr()
+                if a < hi and lo < a + op.numel() * op.element_size():
+                    return False
     return True
 
 
@@ -717,11 +725,52 @@ def _dw_gemm(A, B, transB=False, target=None):
         # the STORAGE is held too (not a tensor: AccumulateGrad counts tensor references only): its memory cannot be
         # handed out again before the grouped launch has written it, and its owner count tells at flush time whether
         # autograd adopted the result (>= 2) or consumed and dropped it (1)
-        _DEFER["items"].append((A, B, out.data_ptr(), zeroed, out.untyped_storage()))
+        # (the last field: the output's leading dimension -- dense here, wider for the slabs of _dw_gemm_slabs)
+        _DEFER["items"].append((A, B, out.data_ptr(), zeroed, out.untyped_storage(), B.shape[1]))
         if leaf is not None:
             _DEFER["leaves"].add(id(leaf))
         return out
     return gemm(A, B, transA=True, transB=transB)
+
+
+def _dw_gemm_slabs(slabs, target=None):
+    """[A_0^T B_0 | A_1^T B_1 | ...]: ONE weight gradient whose column slabs are products of their own (the decoder's
+    dW = [G_c^T x_c | g^T skip], coarse rows beside fine rows). slabs = [(A_i [Kd_i, M], B_i [Kd_i, n_i])], every Kd_i > 0.
+    The rules of _dw_gemm hold for the tensor as a whole: one adopted tensor and one recorded leaf, one table entry per slab
+    of more than 16 columns (narrower slabs run in line into their window), zero-initialised when ANY slab's plan splits
+    with atomics."""
+    leaf = target if (target is not None and target.is_leaf) else None
+    defer = _DEFER["on"] and _HAS_USE_COUNT
+    if _DEFER["on"] and leaf is not None:
+        if id(leaf) in _DEFER["leaves"]:
+            raise RuntimeError("defer_weight_grads: the same parameter receives two weight gradients inside one scope "
+                               "(shared weights): run this backward without the scope (MVK_DEFER_DW=0)")
+        if leaf.grad is not None:
+            defer = False
+    slabs = [(_f32c(A), _f32c(B)) for A, B in slabs]
+    dev, M = slabs[0][0].device, slabs[0][0].shape[1]
+    ld = sum(B.shape[1] for _, B in slabs)
+    grouped = [defer and B.shape[1] > 16 for _, B in slabs]
+    if sum(grouped) + len(_DEFER["items"]) > _DW_MAX:
+        grouped = [False] * len(slabs)
+    split_arena_prepare(dev)
+    ordered = bool(lib().mvk_gemm_split_ordered())
+    zeroed = not ordered and any(
+        (lib().mvk_gemm_f32_tn_grouped_split(M, B.shape[1], A.shape[0]) if gr else gemm_plan(M, B.shape[1], A.shape[0])[0]) > 1
+        for (A, B), gr in zip(slabs, grouped))
+    out = _zeros((M, ld), dev) if zeroed else torch.empty((M, ld), device=dev, dtype=torch.float32)
+    storage = out.untyped_storage() if any(grouped) else None     # ONE owner for all the slabs (see _dw_gemm, _flush_deferred)
+    col0 = 0
+    for (A, B), gr in zip(slabs, grouped):
+        ptr = out.data_ptr() + 4 * col0
+        if gr:
+            _DEFER["items"].append((A, B, ptr, zeroed, storage, ld))
+        else:
+            check(lib().mvk_gemm_f32_tn_ldc(_p(A), _p(B), C.c_void_p(ptr), M, B.shape[1], A.shape[0], ld, _stream()))
+        col0 += B.shape[1]
+    if any(grouped) and leaf is not None:
+        _DEFER["leaves"].add(id(leaf))
+    return out
 
 
 # --------------------------------------------------------------------------------------------
@@ -1486,9 +1535,42 @@ class _UpsampleCatFn(torch.autograd.Function):
         return dx, None, d_skip
 
 
+# The decoder's unary layers as two products: by linearity
+#   cat([x_c[idx], skip]) . W^T = (x_c . W[:, :C1]^T)[idx] + skip . W[:, C1:]^T
+# so the upsampled half is multiplied at COARSE rows (every level keeps ~1/4.4 of the points) and the concatenation is
+# never built. MVK_DECODER_SPLIT=0 (or ops.DECODER_SPLIT = False) keeps the concatenated form.
+DECODER_SPLIT = os.environ.get("MVK_DECODER_SPLIT", "1") != "0"
+
+
+def _nt_ldb_add(A, W, col0, Kd, addend=None, stats_n_valid=None, finish=None):
+    """A [M,Kd] . W[:, col0:col0+Kd]^T (+ src[idx[m]] for addend = (src [ns,N], idx, i64, stride)) with the statistics
+    epilogue / finish of _product (mvk_gemm_f32_nt_ldb_add): returns (C, BnStats or None)."""
+    M, N = A.shape[0], W.shape[0]
+    split_arena_prepare(A.device)
+    stats_ok = stats_n_valid is not None and M <= _STATS_EPILOGUE_ROWS
+    if finish is None:
+        stats_ok = stats_ok and M > bn_single_launch_rows(N)
+    split, rows = gemm_plan(M, N, Kd, None, stats_ok)
+    out = _split_out((M, N), A.device, split)
+    part = torch.empty(((M + rows - 1) // rows, 2, N), device=A.device, dtype=torch.float32) if rows > 0 else None
+    fin = done = None
+    if finish is not None and part is not None:
+        fin, done = _fin_struct(finish, N, A.device)
+    src, idx, i64, stride = addend if addend is not None else (None, None, 0, 1)
+    check(lib().mvk_gemm_f32_nt_ldb_add(_p(A), _p(W), int(col0), W.shape[1], _p(out), M, N, int(Kd), _p(src), _p(idx), int(i64),
+                                        int(stride), src.shape[0] if src is not None else 0, _p(part),
+                                        _p(stats_n_valid) if part is not None else None,
+                                        C.byref(fin) if fin is not None else None, _stream()))
+    return out, (BnStats(part, rows, done) if part is not None else None)
+
+
 class _UpsampleCatLinearFn(torch.autograd.Function):
-    """linear(cat([closest_pool(x, inds), skip], 1), W): the decoder's upsampling, concatenation and unary layer. Forward:
-    the fused gather + concatenation, then the GEMM (statistics epilogue as in linear()). Backward: ONE product for both
+    """linear(cat([closest_pool(x, inds), skip], 1), W): the decoder's upsampling, concatenation and unary layer.
+    Split form (DECODER_SPLIT, the default): forward Yc = x W[:, :C1]^T at coarse rows, then y = skip W[:, C1:]^T + Yc[idx]
+    with the statistics epilogue as in linear() -- two launches, no concatenation. Backward: G_c = the gradient rows summed
+    per coarse point, then dx = G_c W[:, :C1] and d_skip = g W[:, C1:] in one pair launch, dW = [G_c^T x | g^T skip] as two
+    deferred products into one tensor.
+    Concatenated form: the fused gather + concatenation, then the GEMM. Backward: ONE product for both
     inputs -- g W is never stored, the GEMM's epilogue scatters its upsampled columns onto dx and writes the skip columns
     (mvk_gemm_f32_scatter_cat) -- and the weight gradient from the saved concatenation."""
 
@@ -1503,6 +1585,19 @@ class _UpsampleCatLinearFn(torch.autograd.Function):
             raise RuntimeError("upsample_cat_linear: the skip features and the upsampling indices differ in length")
         stride = inds2d.shape[1] if inds2d.dim() == 2 else 1
         C1, C2 = x.shape[1], skip.shape[1]
+        ctx.split_form = bool(DECODER_SPLIT and Nq > 0 and x.shape[0] > 0 and C1 > 0 and C2 > 0 and W.shape[0] > 0)
+        if ctx.split_form:
+            W = _f32c(W)
+            if W.shape[1] != C1 + C2:
+                raise RuntimeError("upsample_cat_linear: the weight has %d input columns, the inputs %d + %d" % (W.shape[1], C1, C2))
+            ctx.set_materialize_grads(False)
+            ctx.save_for_backward(x, skip, W, inds2d)
+            ctx.dims = (x.shape[0], C1, C2, stride, i64)
+            Yc, _ = _nt_ldb_add(x, W, 0, C1)
+            y, st = _nt_ldb_add(skip, W, C1, C2, (Yc, inds2d, i64, stride), stats_n_valid, finish)
+            if st is not None:
+                ctx.mark_non_differentiable(st.partials)
+            return y, st
         cat = torch.empty((Nq, C1 + C2), device=x.device, dtype=torch.float32)
         check(lib().mvk_gather_rows_cat_fwd(_p(x), x.shape[0], C1, _p(inds2d), i64, Nq, stride, _p(skip), C2, _p(cat),
                                             _stream()))
@@ -1515,7 +1610,49 @@ class _UpsampleCatLinearFn(torch.autograd.Function):
         return y, st
 
     @staticmethod
+    def _backward_split(ctx, g):
+        x, skip, W, inds2d = ctx.saved_tensors
+        ns, C1, C2, stride, i64 = ctx.dims
+        need_x, need_skip, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        g = _f32c(g)
+        Nq, N = g.shape
+        split_arena_prepare(g.device)
+        det = False
+        if is_deterministic():
+            det = ctx.rev is not None and ctx.rev.shape[0] >= ns
+            if not det:
+                _no_reverse_list("a closest_pool / upsampling matrix")
+        Gc = None
+        if need_x or need_w:
+            # G_c[j] = the sum of the gradient rows of coarse point j's fine points: a gather over the reverse list in a fixed
+            # order, or the atomic row scatter (shadow indices dropped; coarse rows nobody points at stay zero)
+            if det:
+                Gc = gather_sum_rows(g, ctx.rev[:ns])
+            else:
+                Gc = _zeros((ns, N), g.device)
+                check(lib().mvk_gather_rows_bwd_ld(_p(g), N, _p(inds2d), i64, Nq, stride, ns, N, _p(Gc), _stream()))
+        dx = d_skip = None
+        if need_x and need_skip and not det:
+            plan = (C.c_int * 3)()
+            check(lib().mvk_gemm_f32_nn_pair_plan(ns, C1, Nq, C2, N, plan))
+            if plan[0]:
+                dx = _split_out((ns, C1), g.device, plan[1])
+                d_skip = _split_out((Nq, C2), g.device, plan[2])
+                check(lib().mvk_gemm_f32_nn_pair(_p(Gc), _p(W), _p(dx), ns, C1, _p(g), C.c_void_p(W.data_ptr() + 4 * C1),
+                                                 _p(d_skip), Nq, C2, N, C1 + C2, _stream()))
+        if need_x and dx is None:
+            dx = gemm_ldb(Gc, W, 0, C1, C1 + C2)
+        if need_skip and d_skip is None:
+            d_skip = gemm_ldb(g, W, C1, C2, C1 + C2)
+        dW = _dw_gemm_slabs([(Gc, x), (g, skip)], target=W) if need_w else None
+        return dx, None, d_skip, dW, None, None
+
+    @staticmethod
     def backward(ctx, g, g_st=None):
+        if g is None:                       # (set_materialize_grads(False): the output was not used)
+            return None, None, None, None, None, None
+        if ctx.split_form:
+            return _UpsampleCatLinearFn._backward_split(ctx, g)
         cat, W, inds2d = ctx.saved_tensors
         ns, C1, C2, stride, i64 = ctx.dims
         g = _f32c(g)
