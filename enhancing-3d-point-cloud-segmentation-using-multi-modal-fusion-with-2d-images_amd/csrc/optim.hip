@@ -3,6 +3,7 @@
 // followed by torch.optim.SGD.step, built at trainer.py:72-79 with two parameter groups; torch semantics with
 // dampening 0, no Nesterov):
 //     g' = clamp(g, -clip, +clip);  d = g' + wd * p;  m = momentum * m + d;  p = p - lr * m
+// A NaN gradient stays NaN through the clamp (the reference's diverged step shows as NaN weights); clip = +inf: no clamp.
 // (a zero-initialised momentum buffer makes the first step m = d, torch's "buf = clone(d)").
 // The step is pure streaming (16 B per parameter read, 8 B written: ~0.6 GB for the 24.4 M-parameter KPFCNN), but
 // as library calls it is ~50 launches (a clamp per tensor + multi-tensor chunks); here a device table of tensor
@@ -21,6 +22,10 @@ struct SgdTensor {          // mirrored by ops.FusedClipSGD (ctypes: 3 pointers,
 
 constexpr int SGD_CHUNK = 4096;   // elements per workgroup: 256 threads x 4 float4
 
+// clamp(g, -clip, clip) as torch.clamp / clip_grad_value_ compute it: a NaN stays a NaN (fminf / fmaxf return their
+// non-NaN operand, which would turn a diverged gradient into -clip), and clip = +inf (no clipping) leaves +-inf alone
+__device__ __forceinline__ float clamp_keep_nan(float g, float clip) { return g < -clip ? -clip : (g > clip ? clip : g); }
+
 __global__ __launch_bounds__(256) void sgd_clip_kernel(const SgdTensor* __restrict__ tab, const int2* __restrict__ chunks,
                                                       float clip, float momentum, int clip_in_place) {
   const int2 c = chunks[blockIdx.x];
@@ -38,8 +43,8 @@ __global__ __launch_bounds__(256) void sgd_clip_kernel(const SgdTensor* __restri
       float4 p = *reinterpret_cast<const float4*>(t.p + e);
       float4 g = *reinterpret_cast<const float4*>(t.g + e);
       float4 m = *reinterpret_cast<const float4*>(t.m + e);
-      g.x = fminf(fmaxf(g.x, -clip), clip); g.y = fminf(fmaxf(g.y, -clip), clip);
-      g.z = fminf(fmaxf(g.z, -clip), clip); g.w = fminf(fmaxf(g.w, -clip), clip);
+      g.x = clamp_keep_nan(g.x, clip); g.y = clamp_keep_nan(g.y, clip);
+      g.z = clamp_keep_nan(g.z, clip); g.w = clamp_keep_nan(g.w, clip);
       if (clip_in_place) *reinterpret_cast<float4*>(const_cast<float*>(t.g) + e) = g;
       m.x = momentum * m.x + (g.x + t.wd * p.x); m.y = momentum * m.y + (g.y + t.wd * p.y);
       m.z = momentum * m.z + (g.z + t.wd * p.z); m.w = momentum * m.w + (g.w + t.wd * p.w);
@@ -48,7 +53,7 @@ __global__ __launch_bounds__(256) void sgd_clip_kernel(const SgdTensor* __restri
       *reinterpret_cast<float4*>(t.p + e) = p;
     } else {
       for (int64_t j = e; j < e + 4 && j < t.n; ++j) {
-        const float g = fminf(fmaxf(t.g[j], -clip), clip);
+        const float g = clamp_keep_nan(t.g[j], clip);
         if (clip_in_place) const_cast<float*>(t.g)[j] = g;
         const float m = momentum * t.m[j] + (g + t.wd * t.p[j]);
         t.m[j] = m;

@@ -19,7 +19,8 @@ assert _REC.itemsize == 40
 
 class FusedClipSGD:
     """groups: list of {"params": [...], optional "lr", "weight_decay"} like torch.optim.SGD.
-    clip_value: the bound of clip_grad_value_ (None / inf: no clipping). clip_in_place also leaves the clamped
+    clip_value: the bound of clip_grad_value_ (None, inf or <= 0: no clipping, an infinite gradient stays infinite; a NaN
+    gradient gives a NaN parameter with or without a bound, like torch). clip_in_place also leaves the clamped
     values in ``.grad`` like clip_grad_value_ does (costs one more store per parameter; off by default)."""
 
     def __init__(self, groups, lr, momentum=0.0, weight_decay=0.0, clip_value=None, clip_in_place=False):
@@ -193,7 +194,7 @@ class FusedClipSGD:
         t = self._cur = cached
         stream = torch.cuda.current_stream()
         check(lib().mvk_sgd_clip_step(C.c_void_p(t["dev"].data_ptr()), C.c_void_p(t["chunks_dev"].data_ptr()), t["n"],
-                                      self.clip if np.isfinite(self.clip) else 3.0e38, self.momentum,
+                                      self.clip, self.momentum,       # inf itself when clipping is off: +-inf stays +-inf
                                       int(self.clip_in_place), C.c_void_p(stream.cuda_stream)))
         if not capturing:
             ev = torch.cuda.Event()
